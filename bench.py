@@ -1,6 +1,15 @@
 """bench.py -- DRRs/sec on the BASELINE.json workloads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|2|3|4|5] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line: the contract's keys
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) and the configuration.
+Everything else described below -- `roofline`, the per-kernel census, `parity`, `cpu_baseline`,
+`reference_cpu`, the short runs of the other configs, `sweep` -- is measured with `--full` only.
+`--dump-outputs DIR` writes what the timed step returned in its last step as DIR/<name>.npy (float32 /
+float64, at most 64 MB; a seeded sample of a larger output): the inputs are seeded, so two builds can be
+compared output for output.
 
 `--config headline` (default; BASELINE.json `metric`; SURVEY.md section 8d common scene): 512^3
 fp32 volume resident in HBM, 256x256 detector (delx 2.4, sdd 1020, AP), Siddon renderer, a batch
@@ -16,12 +25,12 @@ Other configs (BASELINE.json `configs`):
   5  4096 candidate poses, forward + per-pose NCC, pose-sharded over the ranks (strong
      scaling), all_gather of the losses                  (configs[4])
 
-N > 1 without a launcher: the script re-executes itself under `python -m torch.distributed.run
---nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL); under a
+N > 1 without a launcher: the script runs itself as a child process under `python -m
+torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL); under a
 launcher (RANK / WORLD_SIZE set) it uses the ranks it is given.  `n_gpus` in the result is the
 world size RCCL actually has.
 
-Rank 0 prints ONE JSON line on stdout: the driver's contract plus
+With --full, rank 0 prints ONE JSON line on stdout: the driver's contract plus
   "roofline":     the dominant kernel's algorithmic byte rate (SURVEY.md section 8d formulas), timed
                   with HIP events around every launch inside the timed region; "roofline.forward":
                   the forward-only kernel (the north star's target) on the step's own poses, primed
@@ -32,7 +41,7 @@ Rank 0 prints ONE JSON line on stdout: the driver's contract plus
                   time, its share of the kernel and the useful fraction (profiles/rNN/issue_bound.json),
                   "roofline.forward_f32": the forward-only kernel on the same 32 poses with
                   brick_storage = "f32" (the volume's own values, as the reference gathers them),
-  "configs":      (default run, one GPU) short runs of BASELINE configs 2, 3 (and its B = 4 timing,
+  "configs":      (--full at the default sizes, one GPU) short runs of BASELINE configs 2, 3 (and its B = 4 timing,
                   "b4"), 4 (the registration loop as one HIP graph per iteration: iterations/s) and 5:
                   ms per step, dominant-kernel rate, parity; "ct": the reference's example geometry
                   on a CT-like 512 x 512 x 133 volume after transform_hu_to_density -- forward and
@@ -59,6 +68,7 @@ import json
 import math
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -301,6 +311,26 @@ REFERENCE_CPU = {  # the UNMODIFIED reference on CPU torch (tools/ref_cpu_baseli
     512: {"value": 0.071, "forward_only": 0.208}, 256: {"value": 0.192, "forward_only": 0.468}}
 
 
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: what the timed step returned in its last step, one DIR/<name>.npy per array in
+    float32 / float64 (other dtypes as float64)."""
+    import numpy as np
+
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes, limit {DUMP_LIMIT}"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step ({total} bytes): {', '.join(sorted(out))} -> {directory}")
+
+
 def free_port():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -376,7 +406,7 @@ class Runtime:
 
 
 # (steps, warmup, priming steps) of a config: the full run, and the short run whose summary the
-# default line carries as "configs" (each short timed region >= ~0.3 s on one MI355X)
+# --full line carries as "configs" (each short timed region >= ~0.3 s on one MI355X)
 FULL = {"headline": (400, 10, 60), "2": (800, 10, 60), "3": (400, 10, 60), "4": (1500, 20, 0), "5": (5, 1, 1)}
 SHORT = {"2": (300, 5, 40), "3": (150, 5, 30), "4": (1000, 20, 0), "5": (2, 0, 1)}
 
@@ -426,7 +456,7 @@ def issue_bound_record(kernel_key, kernel_ms, visits=None):
 
 def run_config(cfg, args, rt, short=False, batch=None, parity=True):
     """One timed run of a BASELINE config on the ranks of `rt`; -> the result dict (rank 0) or
-    None.  short: few steps, no CPU baseline -- the summaries of the default line (batch: poses per
+    None.  short: few steps, no CPU baseline -- the summaries of the --full line (batch: poses per
     step of such a run, e.g. config 3 at B = 4; parity = False: timing only)."""
     on_gpu, world, rank, device, dist = rt.on_gpu, rt.world, rt.rank, rt.device, rt.dist
     fence, fence_wait, timer = rt.fence, rt.fence_wait, rt.timer
@@ -437,6 +467,7 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
     from diffdrr_amd.data import make_subject, noise_volume, synthetic_subject
 
     top = not short  # the run the command line asked for
+    lean = top and not args.full  # a plain run: the headline figure and nothing else
     sized = top or (cfg == "5" and args.sweep_poses is not None)  # (the harness test's small sweep)
     D = (args.size if sized else None) or (256 if cfg == "2" else 512)
     H = (args.det if sized else None) or (512 if cfg == "3" else 256)
@@ -500,6 +531,9 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
                 pending[:] = [dist.all_gather_into_tensor(gathered, loss.detach(), async_op=True)]
             return loss
 
+        def outputs(last):  # what a caller of the step receives: per-pose NCC, 6-DoF pose gradients
+            return {"ncc_per_pose": last, "grad_rot": rot.grad, "grad_xyz": xyz.grad}
+
         units_per_step, unit, scaling = world * B, "DRRs/s", "weak"
         metric = f"DRRs/sec fwd+bwd, {D}^3 vol -> {H}^2 det, batched poses"
         workload = (f"{D}^3 fp32 noise volume -> {H}x{H} detector, Siddon forward + backward w.r.t. "
@@ -520,6 +554,13 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
             (img * go).sum().backward()
             keep["img"] = img
             return img.detach().sum().reshape(1)
+
+        def outputs(last):
+            # the image and the volume gradient (D^3 floats: a fixed, seeded sample of it)
+            g = drr.density.grad.reshape(-1)
+            idx = torch.randint(0, g.numel(), (min(g.numel(), 1 << 20),), generator=torch.Generator().manual_seed(11))
+            return {"image": keep["img"], "volume_grad_sample": g[idx.to(g.device)],
+                    "volume_grad_sample_index": idx}
 
         units_per_step, unit, scaling = world * B, "DRRs/s", "weak"
         metric = f"DRRs/sec fwd+bwd incl. volume gradient, {D}^3 vol -> {H}^2 det, trilinear {P} samples/ray"
@@ -584,6 +625,9 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
             opt.step()
             return loss.detach().reshape(1)
 
+        def outputs(last):  # the similarity of the iteration and the pose Adam left behind
+            return {"ncc": last, "rotation": reg.rotation, "translation": reg.translation}
+
         units_per_step, unit, scaling = world, "iterations/s", "weak"
         metric = f"registration iterations/sec, {D}^3 vol -> {H}^2 det, SE(3) gradient ascent on NCC"
         workload = (f"{D}^3 fp32 phantom volume -> {H}x{H} detector, Siddon "
@@ -603,6 +647,9 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
             vals = ddist.sweep(drr, ncc, fixed, rot0, xyz0, chunk=512)  # all_gather inside
             keep["vals"] = vals
             return vals
+
+        def outputs(last):  # the similarity of every candidate pose
+            return {"ncc_per_pose": last}
 
         units_per_step, unit, scaling = B, "DRRs/s", "strong"
         metric = f"DRRs/sec forward + per-pose NCC, {D}^3 vol -> {H}^2 det, {B} candidate poses sharded"
@@ -632,19 +679,22 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
         step()
     fence(pending)
     pending.clear()
-    timer.enabled, timer.only = True, (dominant if cfg != "4" else None)
+    # (a plain run carries no HIP events: its per-kernel figures are not reported)
+    timer.enabled, timer.only = not lean, (dominant if cfg != "4" else None)
     t0 = time.perf_counter()
     for _ in range(steps):
         last = step()
     fence(pending)
     dt = time.perf_counter() - t0
     timer.enabled, timer.only = False, None
+    if top and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs(last))
     # (the collector stays off for the legs that follow -- forward-only launches between HIP events,
     # the other configs: every run_config collects once, up front)
     assert torch.isfinite(last).all()
     # the step's other kernels: a few steps of their own, every launch but the dominant one timed
     census_steps = 0
-    if cfg != "4":
+    if cfg != "4" and not lean:
         census_steps = min(steps, 30)
         timer.enabled, timer.skip = True, dominant
         for _ in range(census_steps):
@@ -654,8 +704,9 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
         timer.enabled, timer.skip = False, None
     if cfg in ("headline", "2"):
         assert torch.isfinite(rot.grad).all() and torch.isfinite(xyz.grad).all()
-        with torch.no_grad():  # (the fused step writes no image: the same poses, rendered once more)
-            images = drr(rot0, xyz0, parameterization="euler_angles", convention="ZXY")
+        if not lean:  # (for parity; the fused step writes no image: the same poses, rendered once more)
+            with torch.no_grad():
+                images = drr(rot0, xyz0, parameterization="euler_angles", convention="ZXY")
         fused_used = not args.unfused and B <= drr.FUSED_NCC_MAX_POSES
         extra["step"] = ("DRR.ncc, fused (at most %d poses per call): ddrr_pose_raygen_forward, the brick kernel "
                          "with its record, ddrr_siddon_ncc_forward; backward: ddrr_siddon_ncc_backward_pose"
@@ -673,7 +724,7 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
     # timed region (same clocks, same caches), primed like the step -- 60 launches, then 30 timed
     # (config 5's 512-pose launches: 4 + 6).
     f_ms, f_n, f_poses = None, 0, 0
-    if on_gpu and cfg in ("headline", "2", "5"):
+    if on_gpu and cfg in ("headline", "2", "5") and not lean:
         nposes5 = min(512, -(-B // world))
         with torch.no_grad():
             fr, fx = (rot0, xyz0) if cfg != "5" else (rot0[:nposes5], xyz0[:nposes5])
@@ -693,7 +744,7 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
     # The same launches from the volume's OWN fp32 values (brick_storage = "f32": what the reference
     # gathers, renderers.py:159-164): the value-faithful figure next to the 16-bit default's.
     f32_ms, f32_n = None, 0
-    if on_gpu and cfg == "headline" and hasattr(drr.renderer, "brick_storage") and args.storage is None:
+    if on_gpu and cfg == "headline" and hasattr(drr.renderer, "brick_storage") and args.storage is None and not lean:
         had = drr.renderer.brick_storage
         drr.renderer.brick_storage = "f32"
         try:
@@ -715,6 +766,7 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
     t_max = torch.tensor([dt], device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
+    if world > 1 and not lean:
         # per-rank picture for the scaling run: timed region, dominant kernel, waits inside fence()
         k_tot, k_cnt = timer.total_ms(dominant)
         mine = torch.tensor([dt, k_tot / max(1, k_cnt), fence_wait["all_gather_s"], fence_wait["barrier_s"]],
@@ -736,6 +788,55 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
         return None
 
     ms_per_step = dt / steps * 1e3
+    result = {
+        "metric": metric,
+        "value": units_per_step * steps / dt,
+        "unit": unit,
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": workload,
+            "baseline_config": cfg,
+            "volume": f"{D}x{D}x{D} f32 ({D ** 3 * 4 / 2 ** 20:.0f} MiB, replicated per GPU)",
+            "detector": f"{H}x{H}",
+            "batch_per_gpu": B if scaling == "weak" else -(-B // world),
+            "global_batch": B * world if scaling == "weak" else B,
+            "parallelism": (f"pose-sharded x{world}, all_gather of per-pose values (RCCL)"
+                            if world > 1 else "single GPU"),
+        },
+    }
+    storage = getattr(drr.renderer, "brick_storage", None)
+    if storage is not None:
+        from diffdrr_amd.renderers import _brick_storage
+
+        used = _brick_storage(drr.density, {"storage": storage})
+        q16 = ("bricks staged as 16-bit block-quantised voxels, one (min, step) per 32x32x64 "
+               "brick, where the brick's range is <= 12x its level (else the brick is rendered from "
+               "its fp32 values: brick_storage_fallbacks), |error| <= brick range / 131070 per "
+               "voxel, fp32 arithmetic (parity block: measured in this run)")
+        result["config"]["brick_storage"] = {
+            "q16": "q16: " + q16,
+            "q16p": "q16p: " + q16 + "; staged from the volume's packed 16-bit bricks, a "
+                    "per-volume layout copy (+52 % of the volume's bytes) built by the first "
+                    "render after the volume changed (here: in the warm-up, +0.35 ms once), "
+                    "like the bricks' (min, max) table",
+        }.get(used, "f32: the volume's own values" + ("" if used == storage else
+              f" (the module's {storage} applies to volumes with >= 4 double bricks per CU)"))
+        fb = ops.brick_fallbacks(drr.density, used) if used != "f32" else None
+        if fb is not None:
+            result["config"]["brick_storage_fallbacks"] = fb[0]
+            result["config"]["bricks"] = fb[1]
+    if lean:  # what follows is --full's: per-kernel figures, parity, baselines
+        result.update(extra)
+        return result
+
     kernel_timing = ("HIP events around every launch of the dominant kernel inside the timed region (the "
                      f"step's other kernels: around every launch in {census_steps} further steps)")
     if cfg in ("headline", "2") and "fused (" in str(extra.get("step", "")):
@@ -866,78 +967,33 @@ def run_config(cfg, args, rt, short=False, batch=None, parity=True):
     log(f"[bench] config {cfg}: step {ms_per_step:.3f} ms | {k_name} {k_ms:.3f} ms per launch, "
         f"{per_step:.1f} launch(es) per step | backward kernels {bwd_ms:.3f} ms per step | "
         f"{per_unit} | {alg_bytes / launch_units / 1e6:.1f} MB algorithmic per DRR")
-    result = {
-        "metric": metric,
-        "value": units_per_step * steps / dt,
-        "unit": unit,
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": workload,
-            "baseline_config": cfg,
-            "volume": f"{D}x{D}x{D} f32 ({D ** 3 * 4 / 2 ** 20:.0f} MiB, replicated per GPU)",
-            "detector": f"{H}x{H}",
-            "batch_per_gpu": B if scaling == "weak" else -(-B // world),
-            "global_batch": B * world if scaling == "weak" else B,
-            "parallelism": (f"pose-sharded x{world}, all_gather of per-pose values (RCCL)"
-                            if world > 1 else "single GPU"),
-        },
-        "roofline": {
-            "kernel": k_name,
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "frac_is": "the contract's A / P: algorithmic (SURVEY 8d) bytes per launch / kernel time / "
-                       "8 TB/s.  `bound` is the wall the contract prices the kernel against; what BINDS "
-                       "it is `limiter` (the bricks are read from LDS: HBM carries `hbm_traffic_frac` "
-                       "of its peak) and `issue_bound` is the distance to that wall",
-            "limiter": "valu_issue",
-            "hbm_traffic_frac": (traffic[0] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic and k_ms else None,
-            "traffic": traffic[0] if traffic else None,
-            "traffic_source": (traffic[1] + " (separate rocprofv3 --pmc passes of this command, "
-                               "committed; not measured in this run)") if traffic else None,
-            "algorithmic_bytes_per_launch": alg_bytes,
-            "algorithmic_bytes_per_unit": per_unit,
-            "units_per_launch": launch_units,
-            "kernel_ms": k_ms,
-            "kernel_timing": kernel_timing,
-            "launches_per_step": per_step,
-            "launches_timed": k_n,
-            "forward": forward,
-            "forward_f32": forward_f32,
-            "kernels": kernels,
-        },
+    result["roofline"] = {
+        "kernel": k_name,
+        "bound": "hbm",
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "frac_is": "the contract's A / P: algorithmic (SURVEY 8d) bytes per launch / kernel time / "
+                   "8 TB/s.  `bound` is the wall the contract prices the kernel against; what BINDS "
+                   "it is `limiter` (the bricks are read from LDS: HBM carries `hbm_traffic_frac` "
+                   "of its peak) and `issue_bound` is the distance to that wall",
+        "limiter": "valu_issue",
+        "hbm_traffic_frac": (traffic[0] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic and k_ms else None,
+        "traffic": traffic[0] if traffic else None,
+        "traffic_source": (traffic[1] + " (separate rocprofv3 --pmc passes of this command, "
+                           "committed; not measured in this run)") if traffic else None,
+        "algorithmic_bytes_per_launch": alg_bytes,
+        "algorithmic_bytes_per_unit": per_unit,
+        "units_per_launch": launch_units,
+        "kernel_ms": k_ms,
+        "kernel_timing": kernel_timing,
+        "launches_per_step": per_step,
+        "launches_timed": k_n,
+        "forward": forward,
+        "forward_f32": forward_f32,
+        "kernels": kernels,
     }
-    storage = getattr(drr.renderer, "brick_storage", None)
-    if storage is not None:
-        from diffdrr_amd.renderers import _brick_storage
-
-        used = _brick_storage(drr.density, {"storage": storage})
-        q16 = ("bricks staged as 16-bit block-quantised voxels, one (min, step) per 32x32x64 "
-               "brick, where the brick's range is <= 12x its level (else the brick is rendered from "
-               "its fp32 values: brick_storage_fallbacks), |error| <= brick range / 131070 per "
-               "voxel, fp32 arithmetic (parity block: measured in this run)")
-        result["config"]["brick_storage"] = {
-            "q16": "q16: " + q16,
-            "q16p": "q16p: " + q16 + "; staged from the volume's packed 16-bit bricks, a "
-                    "per-volume layout copy (+52 % of the volume's bytes) built by the first "
-                    "render after the volume changed (here: in the warm-up, +0.35 ms once), "
-                    "like the bricks' (min, max) table",
-        }.get(used, "f32: the volume's own values" + ("" if used == storage else
-              f" (the module's {storage} applies to volumes with >= 4 double bricks per CU)"))
-        fb = ops.brick_fallbacks(drr.density, used) if used != "f32" else None
-        if fb is not None:
-            result["config"]["brick_storage_fallbacks"] = fb[0]
-            result["config"]["bricks"] = fb[1]
     if world == 1 and cfg in ("headline", "2") and not (top and args.no_cpu_baseline):
         if top:
             result["cpu_baseline"], result["parity"] = cpu_baseline_and_parity(
@@ -1292,7 +1348,7 @@ def guarded_run(world, name, fn):
 
 
 def summary_of(res):
-    """What the default line keeps of a short config run."""
+    """What the --full line keeps of a short config run."""
     rf = res["roofline"]
     out = {"metric": res["metric"], "value": res["value"], "unit": res["unit"], "steps": res["steps"],
            "ms_per_step": res["ms_per_step"], "scaling": res["scaling"],
@@ -1339,27 +1395,11 @@ def _cap(s, n):
     return s if not isinstance(s, str) or len(s) <= n else s[:n - 3] + "..."
 
 
-def compact_line(full, limit=LINE_LIMIT):
-    """The ONE line rank 0 prints on stdout, from the full record (`bench_full.json`, also on
-    stderr): the driver's contract keys, `roofline`, `cpu_baseline`, `reference_cpu`, the headline
-    parity numbers and a few numbers per config -- at most `limit` bytes whatever the run (sections
-    are dropped, least important first, until it fits; tests/test_bench_line.py).  Names: `frac` is
-    the contract's A / P (algorithmic bytes over kernel time over the HBM peak) and appears only
-    where it cannot exceed 1; the same quotient for kernels that skip work the count includes
-    (all-zero bricks of a CT, bytes served by LDS) is called `work_rate`."""
+def _roofline_line(full):
+    """`roofline` of the line (runs with --full)."""
     rf = full["roofline"]
     kern0 = (rf.get("kernels") or [{}])[0]
     ib = kern0.get("issue_bound") or {}
-    line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-                                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in full}
-    cfg = dict(_pick(full["config"], "baseline_config", "volume", "detector", "batch_per_gpu", "global_batch",
-                     "parallelism", "brick_storage_fallbacks", "bricks"))
-    cfg["workload"] = _cap(full["config"]["workload"], 200)
-    if "brick_storage" in full["config"]:
-        cfg["brick_storage"] = full["config"]["brick_storage"].split(":")[0]
-    if "step" in full:
-        cfg["step"] = _cap(full["step"], 60)
-    line["config"] = {"workload": cfg.pop("workload"), **cfg}
     r = _pick(rf, "kernel", "bound", "achieved", "peak", "unit", "frac")
     r["traffic"] = rf.get("traffic")
     r.update(_pick(rf, "kernel_ms", "algorithmic_bytes_per_launch", "units_per_launch", "launches_timed"))
@@ -1385,7 +1425,30 @@ def compact_line(full, limit=LINE_LIMIT):
     r["other_kernels_ms_per_step"] = {
         k["kernel"].replace("ddrr_", ""): k["kernel_ms"] * k["launches_per_step"]
         for k in (rf.get("kernels") or [])[1:6]}
-    line["roofline"] = r
+    return r
+
+
+def compact_line(full, limit=LINE_LIMIT, full_record=True):
+    """The ONE line rank 0 prints on stdout, from the full record (`bench_full.json`, also on
+    stderr): the driver's contract keys, `roofline`, `cpu_baseline`, `reference_cpu`, the headline
+    parity numbers and a few numbers per config -- at most `limit` bytes whatever the run (sections
+    are dropped, least important first, until it fits; tests/test_bench_line.py).  Names: `frac` is
+    the contract's A / P (algorithmic bytes over kernel time over the HBM peak) and appears only
+    where it cannot exceed 1; the same quotient for kernels that skip work the count includes
+    (all-zero bricks of a CT, bytes served by LDS) is called `work_rate`.  A plain run's record
+    (no --full) has only the contract's keys and the configuration, and so has its line."""
+    line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in full}
+    cfg = dict(_pick(full["config"], "baseline_config", "volume", "detector", "batch_per_gpu", "global_batch",
+                     "parallelism", "brick_storage_fallbacks", "bricks"))
+    cfg["workload"] = _cap(full["config"]["workload"], 200)
+    if "brick_storage" in full["config"]:
+        cfg["brick_storage"] = full["config"]["brick_storage"].split(":")[0]
+    if "step" in full:
+        cfg["step"] = _cap(full["step"], 60)
+    line["config"] = {"workload": cfg.pop("workload"), **cfg}
+    if "roofline" in full:
+        line["roofline"] = _roofline_line(full)
     if "cpu_baseline" in full:
         cb = dict(full["cpu_baseline"])
         cb["sample"] = _cap(cb.get("sample"), 160)
@@ -1459,7 +1522,8 @@ def compact_line(full, limit=LINE_LIMIT):
         configs[name] = e
     if configs:
         line["configs"] = configs
-    line["full_record"] = "bench_full.json (beside bench.py) and stderr"
+    if full_record:
+        line["full_record"] = "bench_full.json (beside bench.py) and stderr"
     exact = {k: line[k] for k in ("value", "ms_per_step") if k in line}  # (the driver's consistency check)
     line = _sig_tree(line)
     line.update(exact)
@@ -1513,7 +1577,17 @@ def main():
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: harness test only (gloo ranks; the kernels are whatever "
                          "DDRR_BENCH_HOOK routes diffdrr_amd.ops to, see tests/test_dist_gloo.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline and per-kernel timings, parity "
+                         "against the oracle, the CPU baseline, the short runs of the other configs and the "
+                         "sweep (`configs`, `sweep`), the full record in bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.device == "cuda":
         # pre-flight, before anything is spawned: more ranks than devices would die one by one in
@@ -1527,21 +1601,23 @@ def main():
                                   "n_gpus_requested": args.gpus, "n_gpus_visible": visible}), flush=True)
             sys.exit(2)
     if args.gpus > 1 and "RANK" not in os.environ:
-        # no launcher: start one rank per GPU ourselves (RCCL needs one process per device)
+        # no launcher: start one rank per GPU ourselves (RCCL needs one process per device), as a
+        # child process -- this one has already opened the devices to count them
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(free_port()), os.path.abspath(__file__), *sys.argv[1:]]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        os.execvpe(cmd[0], cmd, env)
+        rc = subprocess.call(cmd, env=env)
+        sys.exit(rc if rc >= 0 else 128 - rc)
 
     rt = Runtime(args)
     if rt.world != args.gpus and rt.rank == 0:
         log(f"note: --gpus {args.gpus}, process group has {rt.world} ranks; reporting n_gpus={rt.world}")
 
     result = run_config(args.config, args, rt)
-    plain_headline = (args.config == "headline" and rt.on_gpu and not args.no_configs
+    plain_headline = (args.full and args.config == "headline" and rt.on_gpu and not args.no_configs
                       and args.size is None and args.det is None and args.batch is None)
-    sweep_only = (args.config == "headline" and not plain_headline and not args.no_configs
+    sweep_only = (args.full and args.config == "headline" and not plain_headline and not args.no_configs
                   and args.sweep_poses is not None)
     if plain_headline or sweep_only:
         # The other BASELINE configs, short, in the driver's own record.  N = 1: configs 2, 3 and 5
@@ -1588,16 +1664,17 @@ def main():
     if rt.rank == 0:
         result["rccl_ranks"] = rt.rccl_ranks  # (ranks counted by an all_reduce of ones on the devices)
         result["devices_visible"] = torch.cuda.device_count() if rt.on_gpu else 0
-        # the full record: a file beside bench.py and stderr, BEFORE the line the driver parses
-        full = json.dumps(result)
-        try:
-            with open(os.path.join(ROOT, "bench_full.json"), "w") as f:
-                f.write(full + "\n")
-        except OSError as exc:
-            log(f"[bench] bench_full.json not written: {exc}")
-        log("[bench] full record: " + full)
-        sys.stderr.flush()
-        print(json.dumps(compact_line(result)), flush=True)
+        if args.full:
+            # the full record: a file beside bench.py and stderr, BEFORE the line the driver parses
+            full = json.dumps(result)
+            try:
+                with open(os.path.join(ROOT, "bench_full.json"), "w") as f:
+                    f.write(full + "\n")
+            except OSError as exc:
+                log(f"[bench] bench_full.json not written: {exc}")
+            log("[bench] full record: " + full)
+            sys.stderr.flush()
+        print(json.dumps(compact_line(result, full_record=args.full)), flush=True)
 
     if rt.world > 1:
         rt.dist.barrier()

@@ -101,6 +101,45 @@ def test_more_ranks_than_devices_is_one_json_error_line_and_rc_2():
     assert "error" in out and out["n_gpus_requested"] == 64 and out["n_gpus_visible"] == torch.cuda.device_count()
 
 
+@pytest.mark.parametrize("config", ["headline", "3"])
+def test_plain_run_prints_the_headline_and_dumps_its_outputs(tmp_path, config):
+    """Without --full the line is the contract's keys and the configuration -- no roofline, parity or
+    side runs --, --steps sets the timed steps, and --dump-outputs writes what the last timed step
+    returned, the same arrays for the same arguments.  CPU stand-in: the host emulation of the
+    kernels (bench.py --device cpu, tests/bench_emu_hook.py); tiny sizes."""
+    import subprocess
+
+    import numpy as np
+
+    env = dict(os.environ, DDRR_BENCH_HOOK="bench_emu_hook",
+               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests"), ROOT, os.environ.get("PYTHONPATH", "")]))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        dumps.append(tmp_path / f"out{run}")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu", "--config", config,
+               "--size", "24", "--det", "16", "--batch", "2", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(dumps[-1])]
+        res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = res.stdout.strip().splitlines()
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        for k in CONTRACT[:-1]:
+            assert k in out, k
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 2 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+        assert not {"roofline", "parity", "cpu_baseline", "reference_cpu", "configs", "sweep"} & set(out)
+    names = {"headline": ["grad_rot", "grad_xyz", "ncc_per_pose"],
+             "3": ["image", "volume_grad_sample", "volume_grad_sample_index"]}[config]
+    assert sorted(p.stem for p in dumps[0].iterdir()) == names
+    for name in names:
+        a, b = np.load(dumps[0] / f"{name}.npy"), np.load(dumps[1] / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
+
+
 def test_a_failing_side_run_is_recorded_not_fatal():
     """`configs.*` of the default line are side runs: on one GPU a failure is recorded in its place (and
     the line keeps its size and its contract keys); with several ranks the exception propagates."""

@@ -195,7 +195,7 @@ def test_bench_harness_spawns_its_ranks(config, extra, world):
     det = "16" if world == 2 else "8"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--device", "cpu",
            "--config", config, "--size", "24", "--det", det, "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", *extra]
+           "--no-cpu-baseline", "--full", *extra]
     if world > 2:
         env["OMP_NUM_THREADS"] = "1"
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)

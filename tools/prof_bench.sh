@@ -4,10 +4,10 @@
 # usage: tools/prof_bench.sh <outdir>
 OUT=$1; mkdir -p "$OUT"; export TMPDIR=/tmp; ROOT=$(pwd)
 # (the bench's own default step count: the same warm clocks as the HIP-event figures of the line)
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/bench_trace" -o bench --output-format csv -- python "$ROOT/bench.py" --no-cpu-baseline --no-configs > "$ROOT/$OUT/bench_line_under_trace.json") > "$OUT/bench_trace.log" 2>&1
+(cd "$TMPDIR" && timeout 300 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/bench_trace" -o bench --output-format csv -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-configs > "$ROOT/$OUT/bench_line_under_trace.json") > "$OUT/bench_trace.log" 2>&1
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_ATOMIC_sum"; do
   n=$(echo $c | cut -d' ' -f1)
-  (cd /tmp && timeout 90 rocprofv3 --pmc $c -d "$ROOT/$OUT/pmc_$n" -o pmc --output-format csv -- python "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-configs) > "$OUT/pmc_$n.log" 2>&1
+  (cd "$TMPDIR" && timeout 90 rocprofv3 --pmc $c -d "$ROOT/$OUT/pmc_$n" -o pmc --output-format csv -- python "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-configs) > "$OUT/pmc_$n.log" 2>&1
 done
 python - "$OUT" <<'PY'
 import csv, glob, os, sys
@@ -16,7 +16,7 @@ out = sys.argv[1]
 rows = []
 for f in glob.glob(os.path.join(out, "bench_trace", "**", "*kernel_stats.csv"), recursive=True):
     rows = list(csv.DictReader(open(f)))
-print("## rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-configs (top kernels)")
+print("## rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-configs (top kernels)")
 for r in rows[:12]:
     print(f"{float(r['AverageNs'])/1e6:9.4f} ms avg  x{r['Calls']:>5}  {float(r['Percentage']):6.2f}%  {r['Name'][:110]}")
 cnt = defaultdict(lambda: defaultdict(list))
@@ -25,7 +25,7 @@ for f in glob.glob(os.path.join(out, "pmc_*", "**", "*counter_collection.csv"), 
         cnt[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 import json
 traffic = {"_comment": "HBM traffic per launch of the brick kernels on bench.py's workload (512^3, 256^2, 32 poses), "
-           "from separate rocprofv3 --pmc passes of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline "
+           "from separate rocprofv3 --pmc passes of `python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "
            "--no-configs` (tools/prof_bench.sh).  bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: FETCH_SIZE counts "
            "half of wide coalesced reads on gfx950 (MI355X_MICROARCH.md, HBM section)."}
 # (the bench line's forward_f32 leg runs the 32^3 fp32 configuration of the same kernel template)
