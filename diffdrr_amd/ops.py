@@ -443,6 +443,10 @@ def siddon_backward_rays(aux, grad_out, source, target, img, *, eps=1e-8, reduce
     g_img = torch.empty(B, N, dtype=torch.float32, device=target.device) if want_img_grad else None
     if _empty(B, N):
         return g_source, g_target, g_img
+    # (named, so that a contiguous copy outlives the launch: the autograd nodes hand back the ray
+    # tensors they were given -- a chunk of a (B, N, 3) target is a strided view)
+    source, target = source.contiguous(), target.contiguous()
+    img = None if img is None else img.contiguous()
     _launch(
         "ddrr_siddon_backward_rays", target.device, aux.data_ptr(), layout, grad_out.data_ptr(), source.data_ptr(),
         source.shape[1], target.data_ptr(), _ptr(img), B, N, float(eps),
@@ -804,6 +808,8 @@ def siddon_forward_channels(volume, labels_u8, n_channels, source, target, img, 
     if _empty(B, N):
         return out
     labels_u8, volume = labels_u8.contiguous(), volume.contiguous()
+    source, target = source.contiguous(), target.contiguous()
+    img = None if img is None else img.contiguous()
     _launch(
         "ddrr_siddon_forward_channels", volume.device, volume.data_ptr(), labels_u8.data_ptr(),
         *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,

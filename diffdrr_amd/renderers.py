@@ -475,8 +475,21 @@ class _SiddonPoseFn(torch.autograd.Function):
             g_M = ops.siddon_backward_pose(aux, grad_out, source, target, img, Mw, Ainv, P,
                                            eps=cfg["eps"], with_img_path=not stop)
         if need_vol and not stop:
+            pm = cfg.get("pixel_mask")
+            if pm is not None:
+                # a subsample rendered through the pixel mask: the pixels that were not drawn are
+                # zeros of the image, not rays (reference drr.py:142-147 scatters the drawn ones)
+                # -- their upstream gradient reaches nothing.  (The record of such a pixel is
+                # zero, so the pose gradient above needs no mask.)
+                grad_out = grad_out * _pixel_mask_bits(pm, grad_out.shape[-1]).to(grad_out.dtype)
             g_vol = _volume_gradient(volume, source, target, img, grad_out, cfg)
         return g_vol, g_M, None, None, None
+
+
+def _pixel_mask_bits(pixel_mask, n_pixels):
+    """``ops.pixel_mask_of``'s int32 words -> (n_pixels,) bool, True at the pixels it holds."""
+    shifts = torch.arange(32, dtype=torch.int32, device=pixel_mask.device)
+    return ((pixel_mask.unsqueeze(-1) >> shifts) & 1).view(-1)[:n_pixels].bool()
 
 
 class _EulerSiddonNccFn(torch.autograd.Function):
