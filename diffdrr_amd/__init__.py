@@ -12,6 +12,7 @@ from .drr import DRR  # noqa: F401
 from .metrics import (  # noqa: F401
     GradientNormalizedCrossCorrelation2d,
     MultiscaleNormalizedCrossCorrelation2d,
+    MutualInformation,
     NormalizedCrossCorrelation2d,
 )
 from .pose import RigidTransform, convert  # noqa: F401

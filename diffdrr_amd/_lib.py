@@ -134,23 +134,32 @@ EXPORTS = ["ddrr_abi_version", "ddrr_last_error", *_SIGNATURES]
 
 class DdrrLibrary:
     """A loaded implementation of the C ABI (the HIP product library; the
-    tests also bind their host emulation build through this class)."""
+    tests also bind their host emulation build through this class).  The
+    MutualInformation library (include/diffdrr_mi_hip.h) is bound by the same
+    class with its own tables (:func:`mi_library`)."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, exports=None, signatures=None, restypes=None, abi_version=None,
+                 prefix: str = "ddrr"):
+        exports = EXPORTS if exports is None else exports
+        signatures = _SIGNATURES if signatures is None else signatures
+        restypes = _RESTYPES if restypes is None else restypes
+        abi_version = ABI_VERSION if abi_version is None else abi_version
         self.path = path
         self.cdll = ctypes.CDLL(path)
-        for name in EXPORTS:
+        for name in exports:
             if not hasattr(self.cdll, name):
                 raise RuntimeError(f"{path} does not export {name}")
-        self.cdll.ddrr_abi_version.restype = c_int
-        self.cdll.ddrr_last_error.restype = ctypes.c_char_p
-        got = self.cdll.ddrr_abi_version()
-        if got != ABI_VERSION:
-            raise RuntimeError(f"{path}: ABI version {got}, expected {ABI_VERSION}")
-        for name, argtypes in _SIGNATURES.items():
+        version = getattr(self.cdll, f"{prefix}_abi_version")
+        version.restype = c_int
+        self._last_error = getattr(self.cdll, f"{prefix}_last_error")
+        self._last_error.restype = ctypes.c_char_p
+        got = version()
+        if got != abi_version:
+            raise RuntimeError(f"{path}: ABI version {got}, expected {abi_version}")
+        for name, argtypes in signatures.items():
             fn = getattr(self.cdll, name)
             fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, c_int)
+            fn.restype = restypes.get(name, c_int)
 
     def query(self, name: str, *args):
         """An entry that returns a value (``_RESTYPES``), not a status."""
@@ -159,7 +168,7 @@ class DdrrLibrary:
     def call(self, name: str, *args):
         rc = getattr(self.cdll, name)(*args)
         if rc != 0:
-            msg = self.cdll.ddrr_last_error().decode(errors="replace")
+            msg = self._last_error().decode(errors="replace")
             raise RuntimeError(f"{name} failed (code {rc}): {msg}")
 
 
@@ -180,3 +189,41 @@ def get_lib() -> DdrrLibrary:
             )
         _lib = DdrrLibrary(LIB_PATH)
     return _lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_mi_hip.so
+# MutualInformation (C ABI: include/diffdrr_mi_hip.h): a library of its own, with its own version
+MI_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_mi_hip.so")
+MI_ABI_VERSION = 1
+MI_MAX_BINS = 256
+
+_MI_SIGNATURES = {
+    "ddrr_mi_workspace_bytes": [_I, _I, _I, _I],
+    "ddrr_mi_state_floats": [_I],
+    "ddrr_mi_forward": [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _F, _I, _P, _L, _P, _P, _P],
+    "ddrr_mi_backward": [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P],
+}
+_MI_RESTYPES = {"ddrr_mi_workspace_bytes": c_long, "ddrr_mi_state_floats": c_long}
+MI_EXPORTS = ["ddrr_mi_abi_version", "ddrr_mi_last_error", *_MI_SIGNATURES]
+
+
+def mi_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_mi_hip.h."""
+    return DdrrLibrary(path, MI_EXPORTS, _MI_SIGNATURES, _MI_RESTYPES, MI_ABI_VERSION, prefix="ddrr_mi")
+
+
+_mi_lib: DdrrLibrary | None = None
+
+
+def get_mi_lib() -> DdrrLibrary:
+    """The MutualInformation library, loaded on first use.  Raises if it has not been built."""
+    global _mi_lib
+    if _mi_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(MI_LIB_PATH):
+            raise RuntimeError(
+                f"{MI_LIB_PATH} is missing: the MutualInformation kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _mi_lib = mi_library(MI_LIB_PATH)
+    return _mi_lib

@@ -1,15 +1,17 @@
 """Image similarities of the registration / sweep paths.
 
 Normalised cross-correlation -- whole-image, patch-wise, multiscale -- and its gradient
-variant (reference ``diffdrr/metrics.py:16-104``); mutual information and the geodesic pose
-metrics are out of scope.  Pinned to ``tests/golden/metrics.npz``, values
-and autograd gradients of the unmodified reference.
+variant (reference ``diffdrr/metrics.py:16-104``), pinned to ``tests/golden/metrics.npz``, values
+and autograd gradients of the unmodified reference; and mutual information (reference
+``metrics.py:110-139``, kornia's ``marginal_pdf`` / ``joint_pdf`` restated), pinned to a float64
+restatement of its formula (tests/test_mutual_information.py).  The geodesic pose metrics are out
+of scope.
 """
 from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class _NCCFn(torch.autograd.Function):
@@ -234,3 +236,84 @@ class MultiscaleNormalizedCrossCorrelation2d(torch.nn.Module):
             else:  # (a tensor weight)
                 total = total + v * w
         return total
+
+
+class _MIFn(torch.autograd.Function):
+    """MutualInformation of single-channel image pairs without the reference's (B, H W, K) kernel-value
+    tensors: ddrr_mi_forward / ddrr_mi_backward (include/diffdrr_mi_hip.h).  x1, x2 (B or 1, H, W) -> (B,)
+    (B given: both images may be one shared image);
+    bins and sigma are the module's buffers, read on the device.  The gradient w.r.t. either image is one
+    launch (the similarity is symmetric: the same kernel with the roles swapped)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, bins, sigma, epsilon, normalize, B):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, state = ops.mi_forward(x1, x2, bins, sigma, epsilon, normalize, B, want_state=want)
+        ctx.B = B
+        ctx.save_for_backward(x1, x2, bins, sigma, state)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x1, x2, bins, sigma, state = ctx.saved_tensors
+        B = ctx.B
+        grads = [None, None]
+        for which, x in ((0, x1), (1, x2)):
+            if ctx.needs_input_grad[which]:
+                gx = ops.mi_backward(x1, x2, bins, sigma, state, g, which, B)
+                grads[which] = gx.sum(0, keepdim=True) if (x.shape[0] == 1 and B != 1) else gx
+        return grads[0], grads[1], None, None, None, None, None
+
+
+def mutual_information(x1, x2, bins, sigma, epsilon=1e-10, normalize=True):
+    """The reference's MutualInformation as a torch composition (kornia's marginal_pdf / joint_pdf
+    restated): x1, x2 (B, 1, H, W) -> (B,).  Materialises (B, H W, K) kernel values."""
+    B = x1.shape[0]
+    k1 = torch.exp(-0.5 * ((x1.reshape(B, -1, 1) - bins) / sigma).pow(2))
+    k2 = torch.exp(-0.5 * ((x2.reshape(B, -1, 1) - bins) / sigma).pow(2))
+    p1 = k1.mean(dim=1)
+    p1 = p1 / (p1.sum(dim=1, keepdim=True) + epsilon)
+    p2 = k2.mean(dim=1)
+    p2 = p2 / (p2.sum(dim=1, keepdim=True) + epsilon)
+    joint = torch.matmul(k1.transpose(1, 2), k2)
+    p12 = joint / (joint.sum(dim=(1, 2)).view(-1, 1, 1) + 1e-10)  # (joint_pdf's own epsilon)
+    h1 = -(p1 * (p1 + epsilon).log2()).sum(dim=1)
+    h2 = -(p2 * (p2 + epsilon).log2()).sum(dim=1)
+    h12 = -(p12 * (p12 + epsilon).log2()).sum(dim=(1, 2))
+    mi = h1 + h2 - h12
+    if normalize:
+        mi = 2 * mi / (h1 + h2)
+    return mi
+
+
+class MutualInformation(torch.nn.Module):
+    """(Normalised) mutual information of two batches of single-channel images from Gaussian-kernel
+    density estimates of their marginal and joint intensity distributions (reference metrics.py:110-139).
+    float32 images on the device take the fused kernels (num_bins <= 256); everything else -- CPU,
+    float64, more bins, ``bins`` / ``sigma`` that require grad (the kernels differentiate the images
+    only) -- the torch composition :func:`mutual_information`."""
+
+    def __init__(self, sigma=0.1, num_bins=256, epsilon=1e-10, normalize=True):
+        super().__init__()
+        self.register_buffer("sigma", torch.tensor(sigma))
+        self.register_buffer("bins", torch.linspace(0.0, 1.0, num_bins))
+        self.epsilon = epsilon
+        self.normalize = normalize
+
+    def forward(self, x1, x2):
+        if x1.shape != x2.shape:
+            raise ValueError(f"Input images must be the same size: {tuple(x1.shape)} and {tuple(x2.shape)}")
+        if x1.dim() != 4 or x1.shape[1] != 1:
+            raise ValueError(f"MutualInformation takes (B, 1, H, W) images, got {tuple(x1.shape)}")
+        B, _, H, W = x1.shape
+        K = self.bins.numel()
+        if (ops.on_device(x2) and x1.device == x2.device == self.bins.device == self.sigma.device
+                and x1.dtype == x2.dtype == self.bins.dtype == self.sigma.dtype == torch.float32
+                and self.sigma.numel() == 1 and 1 <= K <= _lib.MI_MAX_BINS and H * W > 0
+                and not (torch.is_grad_enabled() and (self.bins.requires_grad or self.sigma.requires_grad))):
+            # an `expand`ed image (the fixed one, usually) is read once per pose from the same memory
+            a = x1[:1, 0] if (B > 1 and x1.stride(0) == 0) else x1[:, 0]
+            b = x2[:1, 0] if (B > 1 and x2.stride(0) == 0) else x2[:, 0]
+            # (the batch size is passed: both images may be expanded)
+            return _MIFn.apply(a, b, self.bins, self.sigma, float(self.epsilon), bool(self.normalize), B)
+        return mutual_information(x1, x2, self.bins, self.sigma, self.epsilon, self.normalize)

@@ -1581,3 +1581,70 @@ def trilinear_samples_general_backward(volume, source, target, img, grad_samples
                 int(bool(align_corners)), _ptr(res["g_source"]), _ptr(res["g_target"]),
                 _ptr(res["g_img"]), _ptr(res["g_alpha"]), _ptr(res["g_volume"]))
     return res
+
+
+# ------------------------------------------------------------------ MutualInformation (libdiffdrr_mi_hip.so)
+def _mi_launch(name, device, *args):
+    """:func:`_launch` through the MutualInformation library (include/diffdrr_mi_hip.h)."""
+    index = device.index
+    current = torch.cuda.current_device()
+    if index is None or index == current:
+        _lib.get_mi_lib().call(name, *args, torch._C._cuda_getCurrentRawStream(current))
+        return
+    with torch.cuda.device(index):
+        _lib.get_mi_lib().call(name, *args, torch._C._cuda_getCurrentRawStream(index))
+
+
+def _mi_image(x, B, N):
+    """(B or 1, H, W) -> (tensor, stride in floats): ONE image shared by the batch (an expanded tensor or
+    a single image) is read in place with stride 0."""
+    if x.shape[0] == 1 and B != 1 or (B > 1 and x.stride(0) == 0):
+        return x[:1].contiguous(), 0
+    return x.contiguous(), N
+
+
+def mi_forward(x1, x2, bins, sigma, epsilon, normalize, B, want_state=True):
+    """MutualInformation (reference metrics.py:110-139) of B image pairs: x1, x2 (B or 1, H, W) fp32 on the
+    device (either or both may be ONE image shared by the batch: the batch size is B, not derived from the
+    shapes); bins (K,), sigma (0-dim): the module's buffers, read on the device.
+    -> (mi (B), state (B, S) | None: what :func:`mi_backward` needs)."""
+    _require_gpu(x2)
+    for x in (x1, x2):
+        if x.shape[0] not in (1, B):
+            raise ValueError(f"image batch {x.shape[0]} is neither 1 nor B = {B}")
+    H, W = x2.shape[-2:]
+    K = bins.numel()
+    a, s1 = _mi_image(x1, B, H * W)
+    b, s2 = _mi_image(x2, B, H * W)
+    bins, sigma = bins.contiguous(), sigma.contiguous()
+    dev = x2.device
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    state = None
+    if want_state:
+        state = torch.empty(B, int(_lib.get_mi_lib().query("ddrr_mi_state_floats", K)), dtype=torch.float32,
+                            device=dev)
+    if B:
+        n = int(_lib.get_mi_lib().query("ddrr_mi_workspace_bytes", B, H, W, K))
+        if n < 0:
+            raise ValueError(_lib.get_mi_lib()._last_error().decode(errors="replace"))
+        ws = torch.empty((n + 15) // 16, 4, dtype=torch.float32, device=dev)  # (16-byte aligned)
+        _mi_launch("ddrr_mi_forward", dev, a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), K,
+                   sigma.data_ptr(), float(epsilon), int(bool(normalize)), ws.data_ptr(), ws.numel() * 4,
+                   out.data_ptr(), _ptr(state))
+    return out, state
+
+
+def mi_backward(x1, x2, bins, sigma, state, g_out, which, B):
+    """g_out[b] * d mi[b] / d x2[b] (which = 1) or / d x1[b] (which = 0), (B, H, W), of :func:`mi_forward`
+    with the same arguments.  A shared differentiated image gets its per-pose gradients (B, H, W)."""
+    H, W = x2.shape[-2:]
+    a, s1 = _mi_image(x1, B, H * W)
+    b, s2 = _mi_image(x2, B, H * W)
+    g_stride = 0 if (g_out.dim() == 0 or (g_out.dim() == 1 and B > 1 and g_out.stride(0) == 0)) else 1
+    g_out = g_out.contiguous() if g_stride else g_out.reshape(-1)[:1].contiguous()
+    grad = torch.empty(B, H, W, dtype=torch.float32, device=x2.device)
+    if B:
+        _mi_launch("ddrr_mi_backward", x2.device, a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(),
+                   bins.numel(), sigma.data_ptr(), state.data_ptr(), int(which), g_out.data_ptr(), g_stride,
+                   grad.data_ptr())
+    return grad
