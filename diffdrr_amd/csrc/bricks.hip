@@ -1327,7 +1327,7 @@ static int siddon_forward_bricks_impl(const float *volume, int dx, int dy, int d
                                       int ranges_valid, void *launch_ws, const unsigned *pixel_mask,
                                       void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
     if (!out && !aux) return fail(-1, "null out pointer");  // (the record alone: ddrr_siddon_ncc_forward forms the image)
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     if (!(record_vmax >= 0.f)) return fail(-1, "record_vmax must be >= 0");
@@ -1410,7 +1410,9 @@ int ddrr_siddon_forward_channels_bricks(const float *volume, const unsigned char
                                         float voxel_shift, float eps, float *out, void *launch_ws,
                                         void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_siddon_forward_channels_bricks (mask_to_channels)"))
+        return rc;
     if (!labels || !out || C < 1) return fail(-1, "null labels/out or C < 1");
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
@@ -1492,7 +1494,9 @@ int ddrr_siddon_forward_channels_bricks_words(const float *words, int dx, int dy
                                               int det_w, int C, float voxel_shift, float eps, float *out,
                                               void *launch_ws, void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(words, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(words, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_siddon_forward_channels_bricks_words (mask_to_channels)"))
+        return rc;
     if (!out || C < 1) return fail(-1, "null out or C < 1");
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
@@ -1513,7 +1517,9 @@ int ddrr_siddon_backward_channels_bricks(const float *volume, const unsigned cha
                                          float voxel_shift, float eps, float *aux, void *launch_ws,
                                          void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_siddon_backward_channels_bricks (mask_to_channels)"))
+        return rc;
     if (!labels || !grad_out || !aux || C < 1) return fail(-1, "null labels/grad_out/aux or C < 1");
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
@@ -1536,7 +1542,9 @@ int ddrr_trilinear_forward_channels_bricks(const float *volume, const unsigned c
                                            const float *alphamax, float *out, void *launch_ws,
                                            void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_trilinear_forward_channels_bricks (mask_to_channels)"))
+        return rc;
     if (!labels || !out || C < 1) return fail(-1, "null labels/out or C < 1");
     if (!alphamin || !alphamax) return fail(-1, "null alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
@@ -1562,7 +1570,9 @@ int ddrr_trilinear_backward_channels_bricks(const float *volume, const unsigned 
                                             const float *alphamax, float *aux, void *launch_ws,
                                             void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_trilinear_backward_channels_bricks (mask_to_channels)"))
+        return rc;
     if (!labels || !grad_out || !aux || C < 1) return fail(-1, "null labels/grad_out/aux or C < 1");
     if (!alphamin || !alphamax) return fail(-1, "null alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
@@ -1589,7 +1599,9 @@ int ddrr_siddon_backward_channels_volume_bricks(const unsigned char *labels, int
     const int N = det_h * det_w;
     if (!g_volume || !grad_out || !labels || C < 1)
         return fail(-1, "null labels / grad_out / g_volume or C < 1");
-    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_siddon_backward_channels_volume_bricks (mask_to_channels)"))
+        return rc;
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
         return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
@@ -1612,7 +1624,7 @@ int ddrr_siddon_backward_volume_bricks(int dx, int dy, int dz, const float *sour
                                        void *launch_ws, void *stream) {
     const int N = det_h * det_w;
     if (!g_volume || !grad_out) return fail(-1, "null grad_out / g_volume");
-    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) {  // nothing contributes: the gradient is zero
@@ -1630,7 +1642,7 @@ int ddrr_trilinear_forward_bricks(const float *volume, int dx, int dy, int dz,
                                   int n_points, const float *alphamin, const float *alphamax,
                                   float *out, float *aux, void *launch_ws, void *stream) {
     const int N = det_h * det_w;
-    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
     if (!out || !alphamin || !alphamax) return fail(-1, "null out / alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
@@ -1680,7 +1692,9 @@ int ddrr_trilinear_backward_channels_volume_bricks(const unsigned char *labels, 
     const int N = det_h * det_w;
     if (!g_volume || !grad_out || !labels || !alphamin || !alphamax || C < 1)
         return fail(-1, "null labels / grad_out / g_volume / alphamin / alphamax or C < 1");
-    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N,
+                              "ddrr_trilinear_backward_channels_volume_bricks (mask_to_channels)"))
+        return rc;
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
@@ -1706,7 +1720,7 @@ int ddrr_trilinear_backward_volume_bricks(int dx, int dy, int dz, const float *s
     const int N = det_h * det_w;
     if (!g_volume || !grad_out || !alphamin || !alphamax)
         return fail(-1, "null grad_out / g_volume / alphamin / alphamax");
-    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N)) return rc;
+    if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
     hipStream_t st = (hipStream_t)stream;

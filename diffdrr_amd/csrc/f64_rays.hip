@@ -120,6 +120,7 @@ int check64(const void *volume, int dx, int dy, int dz, const void *source, int 
             const void *target, int B, int N) {
     if (!volume || !source || !target) return fail(-1, "null pointer");
     if (dx < 1 || dy < 1 || dz < 1) return fail(-1, "volume dims must be positive");
+    if (int rc = check_volume(dx, dy, dz, "the float64 path (ddrr_*_f64)")) return rc;
     if (B < 0 || N < 0) return fail(-1, "negative batch or ray count");
     if (src_n != 1 && src_n != N) return fail(-1, "src_n must be 1 or N");
     return 0;

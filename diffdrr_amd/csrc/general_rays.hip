@@ -128,6 +128,7 @@ int check_gen(const void *volume, int dx, int dy, int dz, const void *source, in
               const void *target, int B, int N, int align_corners) {
     if (!volume || !source || !target) return fail(-1, "null pointer");
     if (dx < 1 || dy < 1 || dz < 1) return fail(-1, "volume dims must be positive");
+    if (int rc = check_volume(dx, dy, dz, "the general path (ddrr_*_general)")) return rc;
     if (B < 0 || N < 0) return fail(-1, "negative batch or ray count");
     if (src_n != 1 && src_n != N) return fail(-1, "src_n must be 1 or N");
     if (align_corners != 0 && align_corners != 1) return fail(-1, "align_corners must be 0 or 1");

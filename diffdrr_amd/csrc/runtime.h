@@ -81,15 +81,18 @@ __device__ __forceinline__ void load_ray(const RayArgs &p, const RayId &id, floa
     }
 }
 
+// `off`: flat voxel index, unsigned (volumes of at most 2^30 voxels) or Off64 (siddon_core.h)
 struct AtomicAdder {
     float *base;
-    __device__ __forceinline__ void operator()(unsigned off, float v) const {
+    template <class Off>
+    __device__ __forceinline__ void operator()(Off off, float v) const {
         unsafeAtomicAdd(base + off, v);  // global_atomic_add_f32, no return
     }
 };
 
 struct NoAdd {
-    __device__ __forceinline__ void operator()(unsigned, float) const {}
+    template <class Off>
+    __device__ __forceinline__ void operator()(Off, float) const {}
 };
 
 // mask_to_channels: the ray owns column out[b, :, n] (zero-filled by the entry point); a run of
@@ -107,8 +110,22 @@ struct ColumnFlush {
     }
 };
 
+// Volume-size caps ("Volume size").  Up to kVoxels32 voxels (4 GiB of fp32)
+// every kernel addresses a volume-sized buffer with 32-bit offsets.  Above it, the per-ray
+// entries launch their Off64 instantiations (wide_offsets) and the brick entries, whose global
+// addresses are 64-bit throughout, run as they are, up to kMaxVoxels; each dim stays below 2^16 and
+// a dy x dz slab within kMaxSlab voxels, so that the signed 32-bit byte step of one voxel along x
+// (and the sum of three steps) cannot overflow.  The routes that keep 32-bit offsets pass their
+// name as `capped` and refuse a larger volume before they launch anything.
+constexpr long kVoxels32 = 1L << 30;
+constexpr long kMaxVoxels = 1L << 34;
+constexpr int kMaxDim = (1 << 16) - 1;
+constexpr long kMaxSlab = 1L << 28;
+inline bool wide_offsets(int dx, int dy, int dz) { return (long)dx * dy * dz > kVoxels32; }
+
+int check_volume(int dx, int dy, int dz, const char *capped);
 int check_common(const float *volume, int dx, int dy, int dz, const float *source, int src_n,
-                 const float *target, int B, int N);
+                 const float *target, int B, int N, const char *capped);
 RayArgs make_args(const float *volume, int dx, int dy, int dz, const float *source, int src_n,
                   const float *target, const float *img, int B, int N, float shift, float eps,
                   int det_h, int det_w, int tile_h, int tile_w);

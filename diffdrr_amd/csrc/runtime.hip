@@ -25,11 +25,24 @@ const char *last_error() { return g_err; }
 
 int g_xcd_swizzle = 1;
 
-int check_common(const float *volume, int dx, int dy, int dz, const float *source, int src_n,
-                 const float *target, int B, int N) {
-    if (!volume || !source || !target) return fail(-1, "null volume/source/target pointer");
+int check_volume(int dx, int dy, int dz, const char *capped) {
     if (dx < 1 || dy < 1 || dz < 1) return fail(-1, "volume dims must be >= 1");
-    if ((long)dx * dy * dz > (1L << 30)) return fail(-1, "volume larger than 2^30 voxels");
+    const long n = (long)dx * dy * dz;
+    if (n <= kVoxels32) return 0;  // (what every entry has always taken)
+    if (capped) {
+        snprintf(g_err, sizeof(g_err),
+                 "%s takes volumes of at most 2^30 voxels (32-bit offsets); this one has %ld", capped, n);
+        return -1;
+    }
+    if (dx > kMaxDim || dy > kMaxDim || dz > kMaxDim || (long)dy * dz > kMaxSlab || n > kMaxVoxels)
+        return fail(-1, "volume larger than the cap of 2^34 voxels (each dim < 2^16, dy * dz <= 2^28)");
+    return 0;
+}
+
+int check_common(const float *volume, int dx, int dy, int dz, const float *source, int src_n,
+                 const float *target, int B, int N, const char *capped) {
+    if (!volume || !source || !target) return fail(-1, "null volume/source/target pointer");
+    if (int rc = check_volume(dx, dy, dz, capped)) return rc;
     if (B < 0 || N < 0) return fail(-1, "negative batch or ray count");
     if (src_n != 1 && src_n != N) return fail(-1, "src_n must be 1 or N");
     return 0;

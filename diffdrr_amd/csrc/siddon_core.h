@@ -62,9 +62,19 @@ DDRR_HD Store global_store(const Dims D) {
     return st;
 }
 
+// Byte offsets (and flat voxel indices) into a volume-sized buffer: `Off` is `unsigned` for
+// volumes of at most 2^30 voxels -- what every kernel has always used -- and Off64 above
+// (runtime.h wide_offsets).  Strides and steps stay signed 32-bit either way; only the running
+// offset and a coordinate times a stride are formed at the width of Off (in its signed twin).
+typedef unsigned long long Off64;
+template <class Off> struct OffSigned;
+template <> struct OffSigned<unsigned> { typedef int T; };
+template <> struct OffSigned<Off64> { typedef long long T; };
+
+template <class Off = unsigned>
 struct GlobalFetch {
     const float *vol;
-    DDRR_HD float operator()(unsigned boff) const {
+    DDRR_HD float operator()(Off boff) const {
         return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(vol) + boff);
     }
 };
@@ -142,17 +152,21 @@ DDRR_HD SiddonSetup siddon_setup_fast(const Box &box, const float s[3], const fl
 }
 
 // State of the 3-way merge once the ray is inside the volume.
-struct SiddonWalk {
+template <class Off = unsigned>
+struct SiddonWalkT {
     float kf[3];    // index of the next plane to be crossed, per axis (as float)
     float dirf[3];  // +1 / -1
     float an[3];    // alpha of that plane
     int dstep[3];   // signed BYTE stride of one voxel step along the axis
-    unsigned off;   // BYTE offset of the current voxel (volume <= 2^30 voxels)
+    Off off;        // BYTE offset of the current voxel
 };
+typedef SiddonWalkT<unsigned> SiddonWalk;
 
-DDRR_HD SiddonWalk siddon_enter(const Store &st, const Box &box, const float s[3], float shift,
-                                const SiddonSetup &q) {
-    SiddonWalk w;
+template <class Off = unsigned>
+DDRR_HD SiddonWalkT<Off> siddon_enter(const Store &st, const Box &box, const float s[3],
+                                      float shift, const SiddonSetup &q) {
+    typedef typename OffSigned<Off>::T S;
+    SiddonWalkT<Off> w;
     const int stride[3] = {st.stride[0], st.stride[1], st.stride[2]};
     w.off = 0u;
 #pragma unroll
@@ -179,7 +193,7 @@ DDRR_HD SiddonWalk siddon_enter(const Store &st, const Box &box, const float s[3
             else if (a_behind > q.entry) i -= di;
             i = i < box.lo[a] ? box.lo[a] : (i > box.hi[a] - 1 ? box.hi[a] - 1 : i);
         }
-        w.off += (unsigned)((i - st.org[a]) * stride[a]);
+        w.off += (Off)((S)(i - st.org[a]) * stride[a]);
         w.kf[a] = (float)(i + (pos ? 1 : 0));
         w.dirf[a] = pos ? 1.f : -1.f;
         w.dstep[a] = pos ? stride[a] : -stride[a];
@@ -188,8 +202,10 @@ DDRR_HD SiddonWalk siddon_enter(const Store &st, const Box &box, const float s[3
     return w;
 }
 
-// Voxel fetch by byte offset: an SGPR base + 32-bit VGPR offset global load.
-DDRR_HD float vox(const float *__restrict__ vol, unsigned boff) {
+// Voxel fetch by byte offset: an SGPR base + 32-bit VGPR offset global load (Off64: a 64-bit
+// VGPR address).
+template <class Off>
+DDRR_HD float vox(const float *__restrict__ vol, Off boff) {
     return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(vol) + boff);
 }
 
@@ -216,18 +232,19 @@ struct SiddonSeg {
     float a_in, a_out, ax_in, ax_out;
 };
 
+template <class Off = unsigned>
 struct SiddonGen {
-    SiddonWalk w;
+    SiddonWalkT<Off> w;
     float a_cur, exit;
     bool live;
     float o0x, o1x, o0z, o1z;  // what the crossing that opened the current segment contributed
     float axis_in;
 };
 
-template <int REDUCE, bool AUX>
-DDRR_HD SiddonSeg siddon_step(SiddonGen &g, const SiddonSetup &q) {
+template <int REDUCE, bool AUX, class Off>
+DDRR_HD SiddonSeg siddon_step(SiddonGen<Off> &g, const SiddonSetup &q) {
     SiddonSeg r;
-    SiddonWalk &w = g.w;
+    SiddonWalkT<Off> &w = g.w;
     const float a_next = min3f(w.an[0], w.an[1], w.an[2]);
     r.seg = g.live ? a_next - g.a_cur : 0.f;
     const float a_lim = g.live ? a_next : -INFINITY;  // dead: no axis advances
@@ -239,8 +256,9 @@ DDRR_HD SiddonSeg siddon_step(SiddonGen &g, const SiddonSetup &q) {
     w.an[0] = plane_alpha(q, 0, w.kf[0]);
     w.an[1] = plane_alpha(q, 1, w.kf[1]);
     w.an[2] = plane_alpha(q, 2, w.kf[2]);
-    const unsigned noff = w.off + (unsigned)((cx ? w.dstep[0] : 0) + (cy ? w.dstep[1] : 0) +
-                                             (cz ? w.dstep[2] : 0));
+    // (the step is summed in 32 bits; Off64 sign-extends it once)
+    const Off noff = w.off + (Off)((cx ? w.dstep[0] : 0) + (cy ? w.dstep[1] : 0) +
+                                   (cz ? w.dstep[2] : 0));
     if (AUX && REDUCE == REDUCE_SUM) {
         // exclusive attribution of a crossing to one axis (priority x > y > z) keeps
         // the telescoping identities sum_a S0_a = 0, sum_a S1_a = I exact at ties
@@ -277,7 +295,7 @@ DDRR_HD SiddonSeg siddon_step(SiddonGen &g, const SiddonSetup &q) {
 // right after it is consumed), on top of the 8 waves per SIMD the 8-wave
 // occupancy provides: the walk is a pure gather whose only lever against HBM /
 // Infinity-Cache latency is the number of outstanding requests.
-template <int REDUCE, bool AUX, bool COUNT, class Fetch>
+template <int REDUCE, bool AUX, bool COUNT, class Off = unsigned, class Fetch>
 DDRR_HD float siddon_walk_t(const Fetch &fetch, const Store &st, const Box &box,
                             const float s[3], float shift, const SiddonSetup &q, float *aux,
                             int *count) {
@@ -287,8 +305,8 @@ DDRR_HD float siddon_walk_t(const Fetch &fetch, const Store &st, const Box &box,
     float S0x = 0.f, S1x = 0.f, S0z = 0.f, S1z = 0.f;             // aux (sum)
     float bV = 0.f, bIn = 0.f, bOut = 0.f, bAin = 0.f, bAout = 0.f;  // aux (max)
     if (q.hit) {
-        SiddonGen g;
-        g.w = siddon_enter(st, box, s, shift, q);
+        SiddonGen<Off> g;
+        g.w = siddon_enter<Off>(st, box, s, shift, q);
         g.a_cur = q.entry;
         g.exit = q.exit;
         g.live = true;
@@ -369,20 +387,20 @@ DDRR_HD float siddon_walk_t(const Fetch &fetch, const Store &st, const Box &box,
     return acc;
 }
 
-template <int REDUCE, bool AUX, bool COUNT, class Fetch>
+template <int REDUCE, bool AUX, bool COUNT, class Off = unsigned, class Fetch>
 DDRR_HD float siddon_forward_ray_t(const Fetch &fetch, const Store &st, const Box &box,
                                    const float s[3], const float t[3], float shift, float eps,
                                    float *aux, int *count) {
     const SiddonSetup q = siddon_setup(box, s, t, shift, eps);
-    return siddon_walk_t<REDUCE, AUX, COUNT>(fetch, st, box, s, shift, q, aux, count);
+    return siddon_walk_t<REDUCE, AUX, COUNT, Off>(fetch, st, box, s, shift, q, aux, count);
 }
 
-template <int REDUCE, bool AUX, bool COUNT>
+template <int REDUCE, bool AUX, bool COUNT, class Off = unsigned>
 DDRR_HD float siddon_forward_ray(const float *__restrict__ vol, const Dims D, const Box &box,
                                  const float s[3], const float t[3], float shift, float eps,
                                  float *aux, int *count) {
-    return siddon_forward_ray_t<REDUCE, AUX, COUNT>(GlobalFetch{vol}, global_store(D), box, s, t,
-                                                    shift, eps, aux, count);
+    return siddon_forward_ray_t<REDUCE, AUX, COUNT, Off>(GlobalFetch<Off>{vol}, global_store(D), box,
+                                                         s, t, shift, eps, aux, count);
 }
 
 // Gradient w.r.t. the voxel-space ray endpoints from the forward record
@@ -425,15 +443,15 @@ DDRR_HD void siddon_backward_ray(const float *aux, const float s[3], const float
 // Volume gradient for one ray: d out / d V[voxel of segment k] = L dalpha_k
 // (sum), or only the arg-max segment (max).  `Add` is the scatter primitive
 // (a hardware fp32 atomic on the GPU).
-template <int REDUCE, class Add>
+template <int REDUCE, class Off = unsigned, class Add>
 DDRR_HD void siddon_scatter_ray(const float *__restrict__ vol, const Dims D, const float s[3],
                                 const float t[3], float shift, float eps, float gl, Add add) {
     const Box box = full_box(D);
     const SiddonSetup q = siddon_setup(box, s, t, shift, eps);
     if (!q.hit) return;
-    SiddonWalk w = siddon_enter(global_store(D), box, s, shift, q);
+    SiddonWalkT<Off> w = siddon_enter<Off>(global_store(D), box, s, shift, q);
     float a_cur = q.entry;
-    unsigned off = w.off;  // bytes
+    Off off = w.off;  // bytes
     const int cap = D.x + D.y + D.z + 3;
     float best = 0.f, bseg = 0.f;
     long boff = -1;
@@ -457,11 +475,11 @@ DDRR_HD void siddon_scatter_ray(const float *__restrict__ vol, const Dims D, con
         w.an[0] = plane_alpha(q, 0, w.kf[0]);
         w.an[1] = plane_alpha(q, 1, w.kf[1]);
         w.an[2] = plane_alpha(q, 2, w.kf[2]);
-        off += (unsigned)((cx ? w.dstep[0] : 0) + (cy ? w.dstep[1] : 0) + (cz ? w.dstep[2] : 0));
+        off += (Off)((cx ? w.dstep[0] : 0) + (cy ? w.dstep[1] : 0) + (cz ? w.dstep[2] : 0));
         a_cur = a_next;
         if (!(a_next < q.exit)) break;
     }
-    if (REDUCE == REDUCE_MAX && boff >= 0) add((unsigned)boff, gl * bseg);
+    if (REDUCE == REDUCE_MAX && boff >= 0) add((Off)boff, gl * bseg);
 }
 
 // mask_to_channels (renderers.py:77-89): per-label line integrals of one ray.
@@ -560,19 +578,24 @@ DDRR_HD GridMap make_gridmap(const Dims D, float shift, bool align_corners) {
     return g;
 }
 
+// (Off: the width of the flat index, see Off64)
+template <class Off = unsigned>
 DDRR_HD float fetch_nearest(const float *__restrict__ vol, const Dims D, float gx, float gy,
                             float gz) {
+    typedef typename OffSigned<Off>::T S;
     const float rx = rintf(gx), ry = rintf(gy), rz = rintf(gz);  // half-to-even == nearbyint
     const bool in = rx >= 0.f && rx < (float)D.x && ry >= 0.f && ry < (float)D.y && rz >= 0.f &&
                     rz < (float)D.z;
     if (!in) return 0.f;
-    return vol[((int)rx * D.y + (int)ry) * D.z + (int)rz];
+    return vol[((S)(int)rx * D.y + (int)ry) * D.z + (int)rz];
 }
 
 // aten grid_sampler_3d bilinear, padding zeros: 8 corners around floor(coord).
 // The two z-neighbours are adjacent in memory and fetched as one pair.
+template <class Off = unsigned>
 DDRR_HD float fetch_trilinear(const float *__restrict__ vol, const Dims D, float gx, float gy,
                               float gz, float grad[3], bool want_grad) {
+    typedef typename OffSigned<Off>::T S;
     const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
     const float ax = gx - fx, ay = gy - fy, az = gz - fz;
     // keep the int conversions in range for far-away samples
@@ -588,7 +611,7 @@ DDRR_HD float fetch_trilinear(const float *__restrict__ vol, const Dims D, float
             const int ox = cxy & 1, oy = cxy >> 1;
             const int x = ix + ox, y = iy + oy;
             if (x < 0 || x >= D.x || y < 0 || y >= D.y) continue;
-            const float *row = vol + (x * D.y + y) * D.z;
+            const float *row = vol + ((S)x * D.y + y) * D.z;
             float v0 = 0.f, v1 = 0.f;
             if (z0in && z1in) {
                 v0 = row[iz];
@@ -616,7 +639,7 @@ DDRR_HD float fetch_trilinear(const float *__restrict__ vol, const Dims D, float
     return T;
 }
 
-template <int REDUCE, int LOOKUP>
+template <int REDUCE, int LOOKUP, class Off = unsigned>
 DDRR_HD float siddon_forward_ray_midpoint(const float *__restrict__ vol, const Dims D,
                                           const float s[3], const float t[3], float shift,
                                           float eps, bool align_corners) {
@@ -655,9 +678,9 @@ DDRR_HD float siddon_forward_ray_midpoint(const float *__restrict__ vol, const D
             const float gz = fmaf(fmaf(mid, d[2], s[2]), g.k[2], g.o[2]);
             float v;
             if (LOOKUP == LOOKUP_MID_TRILINEAR)
-                v = fetch_trilinear(vol, D, gx, gy, gz, nullptr, false);
+                v = fetch_trilinear<Off>(vol, D, gx, gy, gz, nullptr, false);
             else
-                v = fetch_nearest(vol, D, gx, gy, gz);
+                v = fetch_nearest<Off>(vol, D, gx, gy, gz);
             const float term = v * (a_next - a_cur);
             if (REDUCE == REDUCE_SUM)
                 acc += term;
@@ -673,8 +696,9 @@ DDRR_HD float siddon_forward_ray_midpoint(const float *__restrict__ vol, const D
 }
 
 // Scatter k * w_c into the 8 corners of a sample (volume gradient).
-template <class Add>
+template <class Off = unsigned, class Add>
 DDRR_HD void scatter_trilinear(const Dims D, float gx, float gy, float gz, float k, Add add) {
+    typedef typename OffSigned<Off>::T S;
     const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
     const float ax = gx - fx, ay = gy - fy, az = gz - fz;
     const int ix = (int)fminf(fmaxf(fx, -2.f), (float)D.x + 1.f);
@@ -686,16 +710,17 @@ DDRR_HD void scatter_trilinear(const Dims D, float gx, float gy, float gz, float
         const int x = ix + ox, y = iy + oy, z = iz + oz;
         if (x < 0 || x >= D.x || y < 0 || y >= D.y || z < 0 || z >= D.z) continue;
         const float w = (ox ? ax : 1.f - ax) * (oy ? ay : 1.f - ay) * (oz ? az : 1.f - az);
-        add((unsigned)((x * D.y + y) * D.z + z), k * w);
+        add((Off)(((S)x * D.y + y) * D.z + z), k * w);
     }
 }
 
-template <class Add>
+template <class Off = unsigned, class Add>
 DDRR_HD void scatter_nearest(const Dims D, float gx, float gy, float gz, float k, Add add) {
+    typedef typename OffSigned<Off>::T S;
     const float rx = rintf(gx), ry = rintf(gy), rz = rintf(gz);
     const bool in = rx >= 0.f && rx < (float)D.x && ry >= 0.f && ry < (float)D.y && rz >= 0.f &&
                     rz < (float)D.z;
-    if (in) add((unsigned)(((int)rx * D.y + (int)ry) * D.z + (int)rz), k);
+    if (in) add((Off)(((S)(int)rx * D.y + (int)ry) * D.z + (int)rz), k);
 }
 
 // Backward of siddon_forward_ray_midpoint (reduce sum): what autograd returns for the
@@ -709,7 +734,7 @@ DDRR_HD void scatter_nearest(const Dims D, float gx, float gy, float gz, float k
 // own axis (tied crossings: one axis, x before y before z).  gl = grad_out * ray length;
 // I is returned for d out / d img; `add(flat voxel index, value)` scatters the volume gradient
 // (the 8 corner weights for the bilinear lookup).
-template <int LOOKUP, bool WANT_VOL, class Add>
+template <int LOOKUP, bool WANT_VOL, class Off = unsigned, class Add>
 DDRR_HD float siddon_backward_ray_midpoint(const float *__restrict__ vol, const Dims D,
                                            const float s[3], const float t[3], float shift,
                                            float eps, bool align_corners, float gl, float gs[3],
@@ -748,7 +773,7 @@ DDRR_HD float siddon_backward_ray_midpoint(const float *__restrict__ vol, const 
             float T, w = 0.f;
             if (LOOKUP == LOOKUP_MID_TRILINEAR) {
                 float dT[3];
-                T = fetch_trilinear(vol, D, gx, gy, gz, dT, true);
+                T = fetch_trilinear<Off>(vol, D, gx, gy, gz, dT, true);
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
                     const float G = dT[a] * g.k[a];  // d T / d x_a
@@ -757,10 +782,10 @@ DDRR_HD float siddon_backward_ray_midpoint(const float *__restrict__ vol, const 
                     Et[a] = fmaf(seg * mid, G, Et[a]);
                 }
                 w *= seg;
-                if (WANT_VOL) scatter_trilinear(D, gx, gy, gz, gl * seg, add);
+                if (WANT_VOL) scatter_trilinear<Off>(D, gx, gy, gz, gl * seg, add);
             } else {
-                T = fetch_nearest(vol, D, gx, gy, gz);
-                if (WANT_VOL) scatter_nearest(D, gx, gy, gz, gl * seg, add);
+                T = fetch_nearest<Off>(vol, D, gx, gy, gz);
+                if (WANT_VOL) scatter_nearest<Off>(D, gx, gy, gz, gl * seg, add);
             }
             I = fmaf(T, seg, I);
             // the crossing that opened this segment

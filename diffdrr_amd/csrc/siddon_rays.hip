@@ -14,8 +14,10 @@ using namespace ddrr_rt;
 namespace {
 
 // ------------------------------------------------------------------ Siddon
+// Off: the width of the voxel offsets (siddon_core.h Off64): `unsigned` for volumes of at most
+// 2^30 voxels, Off64 above -- chosen per launch (runtime.h wide_offsets, DDRR_LAUNCH_OFF).
 
-template <int REDUCE, bool AUX, bool COUNT>
+template <int REDUCE, bool AUX, bool COUNT, class Off>
 __global__ __launch_bounds__(kBlock) void siddon_fwd_kernel(RayArgs p, float *__restrict__ out,
                                                             float *__restrict__ aux,
                                                             int *__restrict__ n_vox) {
@@ -25,8 +27,8 @@ __global__ __launch_bounds__(kBlock) void siddon_fwd_kernel(RayArgs p, float *__
     load_ray(p, id, s, t);
     float rec[SIDDON_AUX];
     int cnt = 0;
-    const float I = siddon_forward_ray<REDUCE, AUX, COUNT>(p.vol, p.D, full_box(p.D), s, t, p.shift,
-                                                           p.eps, rec, &cnt);
+    const float I = siddon_forward_ray<REDUCE, AUX, COUNT, Off>(p.vol, p.D, full_box(p.D), s, t,
+                                                                p.shift, p.eps, rec, &cnt);
     const float L = p.img ? p.img[id.r] : 1.f;
     out[id.r] = L * I;
     if (AUX) {
@@ -37,15 +39,15 @@ __global__ __launch_bounds__(kBlock) void siddon_fwd_kernel(RayArgs p, float *__
     if (COUNT) n_vox[id.r] = cnt;
 }
 
-template <int REDUCE, int LOOKUP>
+template <int REDUCE, int LOOKUP, class Off>
 __global__ __launch_bounds__(kBlock) void siddon_fwd_mid_kernel(RayArgs p, int align_corners,
                                                                 float *__restrict__ out) {
     const RayId id = ray_id(p);
     if (id.n < 0) return;
     float s[3], t[3];
     load_ray(p, id, s, t);
-    const float I = siddon_forward_ray_midpoint<REDUCE, LOOKUP>(p.vol, p.D, s, t, p.shift, p.eps,
-                                                                align_corners != 0);
+    const float I = siddon_forward_ray_midpoint<REDUCE, LOOKUP, Off>(p.vol, p.D, s, t, p.shift,
+                                                                     p.eps, align_corners != 0);
     const float L = p.img ? p.img[id.r] : 1.f;
     out[id.r] = L * I;
 }
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void siddon_bwd_rays_kernel(
     if (g_img) g_img[r] = g * rec[0];
 }
 
-template <int REDUCE>
+template <int REDUCE, class Off>
 __global__ __launch_bounds__(kBlock) void siddon_bwd_volume_kernel(
     RayArgs p, const float *__restrict__ grad_out, float *__restrict__ g_volume) {
     const RayId id = ray_id(p);
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void siddon_bwd_volume_kernel(
     const float L = p.img ? p.img[id.r] : 1.f;
     const float gl = grad_out[id.r] * L;
     if (gl == 0.f) return;
-    siddon_scatter_ray<REDUCE>(p.vol, p.D, s, t, p.shift, p.eps, gl, AtomicAdder{g_volume});
+    siddon_scatter_ray<REDUCE, Off>(p.vol, p.D, s, t, p.shift, p.eps, gl, AtomicAdder{g_volume});
 }
 
 // mask_to_channels (renderers.py:77-89): the ray owns column out[b, :, n]; runs
@@ -224,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void siddon_segments_bwd_kernel(
 
 // Backward of the midpoint-lookup forms (align_corners = True, mode "bilinear"): one more walk
 // (siddon_backward_ray_midpoint), no record.
-template <int LOOKUP, bool WANT_VOL>
+template <int LOOKUP, bool WANT_VOL, class Off>
 __global__ __launch_bounds__(kBlock) void siddon_bwd_mid_kernel(
     RayArgs p, const float *__restrict__ grad_out, int align_corners, float *__restrict__ g_source,
     float *__restrict__ g_target, float *__restrict__ g_img, float *__restrict__ g_volume) {
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void siddon_bwd_mid_kernel(
     const float L = p.img ? p.img[id.r] : 1.f;
     const float g = grad_out[id.r];
     float gs[3], gt[3];
-    const float I = siddon_backward_ray_midpoint<LOOKUP, WANT_VOL>(
+    const float I = siddon_backward_ray_midpoint<LOOKUP, WANT_VOL, Off>(
         p.vol, p.D, s, t, p.shift, p.eps, align_corners != 0, g * L, gs, gt, AtomicAdder{g_volume});
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -254,7 +256,7 @@ int ddrr_siddon_forward(const float *volume, int dx, int dy, int dz, const float
                         float voxel_shift, float eps, int reduce_mode, int lookup_mode,
                         int align_corners, int det_h, int det_w, int tile_h, int tile_w,
                         float *out, float *aux, int *n_vox, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N, nullptr)) return rc;
     if (!out) return fail(-1, "null out pointer");
     if (reduce_mode != DDRR_REDUCE_SUM && reduce_mode != DDRR_REDUCE_MAX)
         return fail(-1, "reduce_mode must be DDRR_REDUCE_SUM or DDRR_REDUCE_MAX");
@@ -263,11 +265,19 @@ int ddrr_siddon_forward(const float *volume, int dx, int dy, int dz, const float
                                 eps, det_h, det_w, tile_h, tile_w);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(grid_for(p)), block(kBlock);
+    const bool wide = wide_offsets(dx, dy, dz);
     if (lookup_mode == DDRR_LOOKUP_STEP) {
         if (align_corners) return fail(-1, "DDRR_LOOKUP_STEP requires align_corners=0");
         const bool sum = reduce_mode == DDRR_REDUCE_SUM;
-#define LAUNCH(R, A, C) \
-    hipLaunchKernelGGL((siddon_fwd_kernel<R, A, C>), grid, block, 0, st, p, out, aux, n_vox)
+#define LAUNCH(R, A, C)                                                                            \
+    do {                                                                                           \
+        if (wide)                                                                                  \
+            hipLaunchKernelGGL((siddon_fwd_kernel<R, A, C, Off64>), grid, block, 0, st, p, out,    \
+                               aux, n_vox);                                                        \
+        else                                                                                       \
+            hipLaunchKernelGGL((siddon_fwd_kernel<R, A, C, unsigned>), grid, block, 0, st, p, out, \
+                               aux, n_vox);                                                        \
+    } while (0)
         if (n_vox) {
             if (aux) return fail(-1, "aux and n_vox cannot be requested together");
             if (sum) LAUNCH(REDUCE_SUM, false, true);
@@ -284,8 +294,15 @@ int ddrr_siddon_forward(const float *volume, int dx, int dy, int dz, const float
         if (aux || n_vox) return fail(-1, "aux / n_vox are only produced by DDRR_LOOKUP_STEP");
         const bool sum = reduce_mode == DDRR_REDUCE_SUM;
         const bool tri = lookup_mode == DDRR_LOOKUP_MID_TRILINEAR;
-#define LAUNCH(R, K) \
-    hipLaunchKernelGGL((siddon_fwd_mid_kernel<R, K>), grid, block, 0, st, p, align_corners, out)
+#define LAUNCH(R, K)                                                                               \
+    do {                                                                                           \
+        if (wide)                                                                                  \
+            hipLaunchKernelGGL((siddon_fwd_mid_kernel<R, K, Off64>), grid, block, 0, st, p,        \
+                               align_corners, out);                                                \
+        else                                                                                       \
+            hipLaunchKernelGGL((siddon_fwd_mid_kernel<R, K, unsigned>), grid, block, 0, st, p,     \
+                               align_corners, out);                                                \
+    } while (0)
         if (sum && tri) LAUNCH(REDUCE_SUM, LOOKUP_MID_TRILINEAR);
         else if (sum) LAUNCH(REDUCE_SUM, LOOKUP_MID_NEAREST);
         else if (tri) LAUNCH(REDUCE_MAX, LOOKUP_MID_TRILINEAR);
@@ -329,21 +346,22 @@ int ddrr_siddon_backward_volume(const float *volume, int dx, int dy, int dz, con
                                 const float *grad_out, int B, int N, float voxel_shift, float eps,
                                 int reduce_mode, int det_h, int det_w, int tile_h, int tile_w,
                                 float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N, nullptr)) return rc;
     if (!grad_out || !g_volume) return fail(-1, "null grad_out / g_volume");
     if (B == 0 || N == 0) return 0;
     const RayArgs p = make_args(volume, dx, dy, dz, source, src_n, target, img, B, N, voxel_shift,
                                 eps, det_h, det_w, tile_h, tile_w);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(grid_for(p)), block(kBlock);
-    if (reduce_mode == DDRR_REDUCE_SUM)
-        hipLaunchKernelGGL((siddon_bwd_volume_kernel<REDUCE_SUM>), grid, block, 0, st, p, grad_out,
-                           g_volume);
-    else if (reduce_mode == DDRR_REDUCE_MAX)
-        hipLaunchKernelGGL((siddon_bwd_volume_kernel<REDUCE_MAX>), grid, block, 0, st, p, grad_out,
-                           g_volume);
-    else
-        return fail(-1, "bad reduce_mode");
+    const bool wide = wide_offsets(dx, dy, dz);
+#define LAUNCH(R, O) \
+    hipLaunchKernelGGL((siddon_bwd_volume_kernel<R, O>), grid, block, 0, st, p, grad_out, g_volume)
+    if (reduce_mode == DDRR_REDUCE_SUM && wide) LAUNCH(REDUCE_SUM, Off64);
+    else if (reduce_mode == DDRR_REDUCE_SUM) LAUNCH(REDUCE_SUM, unsigned);
+    else if (reduce_mode == DDRR_REDUCE_MAX && wide) LAUNCH(REDUCE_MAX, Off64);
+    else if (reduce_mode == DDRR_REDUCE_MAX) LAUNCH(REDUCE_MAX, unsigned);
+    else return fail(-1, "bad reduce_mode");
+#undef LAUNCH
     return finish("ddrr_siddon_backward_volume");
 }
 
@@ -352,7 +370,9 @@ int ddrr_siddon_forward_channels(const float *volume, const unsigned char *label
                                  const float *img, int B, int N, int C, float voxel_shift,
                                  float eps, int det_h, int det_w, int tile_h, int tile_w,
                                  float *out, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_siddon_forward_channels (mask_to_channels)"))
+        return rc;
     if (!labels || !out || C < 1) return fail(-1, "null labels/out or C < 1");
     if (B == 0 || N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
@@ -371,7 +391,9 @@ int ddrr_siddon_backward_channels(const float *volume, const unsigned char *labe
                                   int B, int N, int C, float voxel_shift, float eps, int det_h,
                                   int det_w, int tile_h, int tile_w, float *g_source,
                                   float *g_target, float *g_img, float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_siddon_backward_channels (mask_to_channels)"))
+        return rc;
     if (!labels || !grad_out || C < 1) return fail(-1, "null labels/grad_out or C < 1");
     if (B == 0 || N == 0) return 0;
     const RayArgs p = make_args(volume, dx, dy, dz, source, src_n, target, img, B, N, voxel_shift,
@@ -385,7 +407,9 @@ int ddrr_siddon_backward_channels(const float *volume, const unsigned char *labe
 int ddrr_siddon_segments(const float *volume, int dx, int dy, int dz, const float *source,
                          int src_n, const float *target, const float *img, int B, int N,
                          float voxel_shift, float eps, float *terms, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_siddon_segments (callable reducefn)"))
+        return rc;
     if (!terms) return fail(-1, "null terms pointer");
     if (B == 0 || N == 0) return 0;
     const RayArgs p = make_args(volume, dx, dy, dz, source, src_n, target, img, B, N, voxel_shift,
@@ -400,7 +424,9 @@ int ddrr_siddon_segments_backward(const float *volume, int dx, int dy, int dz, c
                                   const float *grad_terms, int B, int N, float voxel_shift,
                                   float eps, float *g_source, float *g_target, float *g_img,
                                   float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_siddon_segments_backward (callable reducefn)"))
+        return rc;
     if (!grad_terms) return fail(-1, "null grad_terms pointer");
     if (B == 0 || N == 0) return 0;
     const RayArgs p = make_args(volume, dx, dy, dz, source, src_n, target, img, B, N, voxel_shift,
@@ -421,7 +447,7 @@ int ddrr_siddon_backward_midpoint(const float *volume, int dx, int dy, int dz, c
                                   const float *grad_out, int B, int N, float voxel_shift,
                                   float eps, int lookup_mode, int align_corners, float *g_source,
                                   float *g_target, float *g_img, float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N, nullptr)) return rc;
     if (!grad_out) return fail(-1, "null grad_out pointer");
     if (lookup_mode != DDRR_LOOKUP_MID_NEAREST && lookup_mode != DDRR_LOOKUP_MID_TRILINEAR)
         return fail(-1, "lookup_mode must be a midpoint lookup");
@@ -430,9 +456,16 @@ int ddrr_siddon_backward_midpoint(const float *volume, int dx, int dy, int dz, c
                                 eps, 0, 0, 1, 64);
     const dim3 grid(grid_for(p)), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH(LK, WV)                                                                          \
-    hipLaunchKernelGGL((siddon_bwd_mid_kernel<LK, WV>), grid, block, 0, st, p, grad_out,         \
-                       align_corners, g_source, g_target, g_img, g_volume)
+    const bool wide = wide_offsets(dx, dy, dz);
+#define LAUNCH(LK, WV)                                                                             \
+    do {                                                                                           \
+        if (wide)                                                                                  \
+            hipLaunchKernelGGL((siddon_bwd_mid_kernel<LK, WV, Off64>), grid, block, 0, st, p,      \
+                               grad_out, align_corners, g_source, g_target, g_img, g_volume);      \
+        else                                                                                       \
+            hipLaunchKernelGGL((siddon_bwd_mid_kernel<LK, WV, unsigned>), grid, block, 0, st, p,   \
+                               grad_out, align_corners, g_source, g_target, g_img, g_volume);      \
+    } while (0)
     const bool tri = lookup_mode == DDRR_LOOKUP_MID_TRILINEAR;
     if (tri && g_volume) LAUNCH(LOOKUP_MID_TRILINEAR, true);
     else if (tri) LAUNCH(LOOKUP_MID_TRILINEAR, false);

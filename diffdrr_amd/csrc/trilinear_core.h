@@ -114,7 +114,7 @@ DDRR_HD void march_exact_coord(const Dims D, float lin, const MarchSetup &q, flo
         gz = un_[2];                                                               \
     }
 
-template <int REDUCE, bool NEAREST>
+template <int REDUCE, bool NEAREST, class Off = unsigned>
 DDRR_HD float trilinear_forward_ray(const float *__restrict__ vol, const Dims D, const float s[3],
                                     const float t[3], float shift, float eps, int P, float amin,
                                     float amax, bool align_corners) {
@@ -128,8 +128,8 @@ DDRR_HD float trilinear_forward_ray(const float *__restrict__ vol, const Dims D,
         float gy = fmaf(fmaf(al, q.d[1], s[1]), g.k[1], g.o[1]);
         float gz = fmaf(fmaf(al, q.d[2], s[2]), g.k[2], g.o[2]);
         DDRR_MARCH_NEAREST_COORD(lin01(m, P, q.lstep))
-        const float v = NEAREST ? fetch_nearest(vol, D, gx, gy, gz)
-                                : fetch_trilinear(vol, D, gx, gy, gz, nullptr, false);
+        const float v = NEAREST ? fetch_nearest<Off>(vol, D, gx, gy, gz)
+                                : fetch_trilinear<Off>(vol, D, gx, gy, gz, nullptr, false);
         if (REDUCE == REDUCE_SUM)
             acc += v;
         else
@@ -250,7 +250,7 @@ struct LabelWeight {
 // reducefn = "max" (renderers.py:178-179): autograd routes the gradient to the arg-max sample
 // alone (the first one on ties).  Index of that sample, or -1 if the maximum is one of the
 // skipped samples outside the volume (value 0, no gradient).
-template <bool NEAREST>
+template <bool NEAREST, class Off = unsigned>
 DDRR_HD int trilinear_argmax_ray(const float *__restrict__ vol, const Dims D, const float s[3],
                                  const float t[3], float shift, float eps, int P, float amin,
                                  float amax, bool align_corners) {
@@ -264,8 +264,8 @@ DDRR_HD int trilinear_argmax_ray(const float *__restrict__ vol, const Dims D, co
         float gy = fmaf(fmaf(al, q.d[1], s[1]), g.k[1], g.o[1]);
         float gz = fmaf(fmaf(al, q.d[2], s[2]), g.k[2], g.o[2]);
         DDRR_MARCH_NEAREST_COORD(lin01(m, P, q.lstep))
-        const float v = NEAREST ? fetch_nearest(vol, D, gx, gy, gz)
-                                : fetch_trilinear(vol, D, gx, gy, gz, nullptr, false);
+        const float v = NEAREST ? fetch_nearest<Off>(vol, D, gx, gy, gz)
+                                : fetch_trilinear<Off>(vol, D, gx, gy, gz, nullptr, false);
         if (v > best) {
             best = v;
             idx = m;
@@ -283,7 +283,7 @@ struct OneSampleWeight {
 
 // Backward of the sum-reduced march for one ray.
 // gl = grad_out * ray length (the ray length alone when `wt` carries the gradient).
-template <bool NEAREST, bool WANT_VOL, class Add, class Weight = UnitWeight>
+template <bool NEAREST, bool WANT_VOL, class Off = unsigned, class Add, class Weight = UnitWeight>
 DDRR_HD MarchGrad trilinear_backward_ray(const float *__restrict__ vol, const Dims D,
                                          const float s[3], const float t[3], float shift,
                                          float eps, int P, float amin, float amax,
@@ -306,11 +306,11 @@ DDRR_HD MarchGrad trilinear_backward_ray(const float *__restrict__ vol, const Di
         DDRR_MARCH_NEAREST_COORD(u)
         const float w = wt(m, u, q);
         if (NEAREST) {
-            sumT = fmaf(w, fetch_nearest(vol, D, gx, gy, gz), sumT);
-            if (WANT_VOL) scatter_nearest(D, gx, gy, gz, k * w, add);
+            sumT = fmaf(w, fetch_nearest<Off>(vol, D, gx, gy, gz), sumT);
+            if (WANT_VOL) scatter_nearest<Off>(D, gx, gy, gz, k * w, add);
         } else {
             float dT[3];
-            sumT = fmaf(w, fetch_trilinear(vol, D, gx, gy, gz, dT, true), sumT);
+            sumT = fmaf(w, fetch_trilinear<Off>(vol, D, gx, gy, gz, dT, true), sumT);
             float ddot = 0.f;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -321,7 +321,7 @@ DDRR_HD MarchGrad trilinear_backward_ray(const float *__restrict__ vol, const Di
             }
             Cd += ddot;
             Cu = fmaf(u, ddot, Cu);
-            if (WANT_VOL) scatter_trilinear(D, gx, gy, gz, k * w, add);
+            if (WANT_VOL) scatter_trilinear<Off>(D, gx, gy, gz, k * w, add);
         }
     }
 #pragma unroll

@@ -10,8 +10,10 @@ using namespace ddrr_rt;
 namespace {
 
 // --------------------------------------------------------------- Trilinear
+// Off: the width of the voxel offsets (siddon_core.h Off64), chosen per launch as in
+// siddon_rays.hip.
 
-template <int REDUCE, bool NEAREST>
+template <int REDUCE, bool NEAREST, class Off>
 __global__ __launch_bounds__(kBlock) void trilinear_fwd_kernel(RayArgs p, int n_points,
                                                                const float *__restrict__ amin,
                                                                const float *__restrict__ amax,
@@ -21,9 +23,9 @@ __global__ __launch_bounds__(kBlock) void trilinear_fwd_kernel(RayArgs p, int n_
     if (id.n < 0) return;
     float s[3], t[3];
     load_ray(p, id, s, t);
-    const float I = trilinear_forward_ray<REDUCE, NEAREST>(p.vol, p.D, s, t, p.shift, p.eps,
-                                                           n_points, amin[0], amax[0],
-                                                           align_corners != 0);
+    const float I = trilinear_forward_ray<REDUCE, NEAREST, Off>(p.vol, p.D, s, t, p.shift, p.eps,
+                                                                n_points, amin[0], amax[0],
+                                                                align_corners != 0);
     const float L = p.img ? p.img[id.r] : 1.f;
     out[id.r] = L * I;
 }
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(kBlock) void trilinear_fwd_channels_kernel(
                            align_corners != 0, ColumnFlush{col, p.N, C, L});
 }
 
-template <bool NEAREST, bool WANT_VOL>
+template <bool NEAREST, bool WANT_VOL, class Off>
 __global__ __launch_bounds__(kBlock) void trilinear_bwd_kernel(
     RayArgs p, const float *__restrict__ grad_out, int n_points, const float *__restrict__ amin,
     const float *__restrict__ amax, int align_corners, float *__restrict__ g_source,
@@ -57,12 +59,12 @@ __global__ __launch_bounds__(kBlock) void trilinear_bwd_kernel(
     const float a0 = amin[0], a1 = amax[0];
     MarchGrad r;
     if (WANT_VOL)
-        r = trilinear_backward_ray<NEAREST, true>(p.vol, p.D, s, t, p.shift, p.eps, n_points, a0,
-                                                  a1, align_corners != 0, g * L,
-                                                  AtomicAdder{g_volume});
+        r = trilinear_backward_ray<NEAREST, true, Off>(p.vol, p.D, s, t, p.shift, p.eps, n_points,
+                                                       a0, a1, align_corners != 0, g * L,
+                                                       AtomicAdder{g_volume});
     else
-        r = trilinear_backward_ray<NEAREST, false>(p.vol, p.D, s, t, p.shift, p.eps, n_points,
-                                                   a0, a1, align_corners != 0, g * L, NoAdd{});
+        r = trilinear_backward_ray<NEAREST, false, Off>(p.vol, p.D, s, t, p.shift, p.eps, n_points,
+                                                        a0, a1, align_corners != 0, g * L, NoAdd{});
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         if (g_source) g_source[id.r * 3 + a] = r.gs[a];
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void trilinear_samples_bwd_kernel(
 
 // reducefn = "max": the gradient of the arg-max sample alone (one march to find it, one for
 // its gradient).
-template <bool NEAREST, bool WANT_VOL>
+template <bool NEAREST, bool WANT_VOL, class Off>
 __global__ __launch_bounds__(kBlock) void trilinear_bwd_max_kernel(
     RayArgs p, const float *__restrict__ grad_out, int n_points, const float *__restrict__ amin,
     const float *__restrict__ amax, int align_corners, float *__restrict__ g_source,
@@ -176,15 +178,15 @@ __global__ __launch_bounds__(kBlock) void trilinear_bwd_max_kernel(
     const float g = grad_out[id.r];
     const float a0 = amin[0], a1 = amax[0];
     const bool ac = align_corners != 0;
-    const OneSampleWeight wt{
-        trilinear_argmax_ray<NEAREST>(p.vol, p.D, s, t, p.shift, p.eps, n_points, a0, a1, ac)};
+    const OneSampleWeight wt{trilinear_argmax_ray<NEAREST, Off>(p.vol, p.D, s, t, p.shift, p.eps,
+                                                                n_points, a0, a1, ac)};
     MarchGrad r;
     if (WANT_VOL)
-        r = trilinear_backward_ray<NEAREST, true>(p.vol, p.D, s, t, p.shift, p.eps, n_points, a0,
-                                                  a1, ac, g * L, AtomicAdder{g_volume}, wt);
+        r = trilinear_backward_ray<NEAREST, true, Off>(p.vol, p.D, s, t, p.shift, p.eps, n_points,
+                                                       a0, a1, ac, g * L, AtomicAdder{g_volume}, wt);
     else
-        r = trilinear_backward_ray<NEAREST, false>(p.vol, p.D, s, t, p.shift, p.eps, n_points, a0,
-                                                   a1, ac, g * L, NoAdd{}, wt);
+        r = trilinear_backward_ray<NEAREST, false, Off>(p.vol, p.D, s, t, p.shift, p.eps, n_points,
+                                                        a0, a1, ac, g * L, NoAdd{}, wt);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         if (g_source) g_source[id.r * 3 + a] = r.gs[a];
@@ -296,7 +298,7 @@ int ddrr_trilinear_forward(const float *volume, int dx, int dy, int dz, const fl
                            const float *alphamax, int mode_nearest, int reduce_mode,
                            int align_corners, int det_h, int det_w, int tile_h, int tile_w,
                            float *out, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N, nullptr)) return rc;
     if (!out || !alphamin || !alphamax) return fail(-1, "null out / alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (B == 0 || N == 0) return 0;
@@ -306,9 +308,16 @@ int ddrr_trilinear_forward(const float *volume, int dx, int dy, int dz, const fl
     const dim3 grid(grid_for(p)), block(kBlock);
     const bool sum = reduce_mode == DDRR_REDUCE_SUM;
     if (!sum && reduce_mode != DDRR_REDUCE_MAX) return fail(-1, "bad reduce_mode");
-#define LAUNCH(R, NN)                                                                          \
-    hipLaunchKernelGGL((trilinear_fwd_kernel<R, NN>), grid, block, 0, st, p, n_points, alphamin, \
-                       alphamax, align_corners, out)
+    const bool wide = wide_offsets(dx, dy, dz);
+#define LAUNCH(R, NN)                                                                              \
+    do {                                                                                           \
+        if (wide)                                                                                  \
+            hipLaunchKernelGGL((trilinear_fwd_kernel<R, NN, Off64>), grid, block, 0, st, p,        \
+                               n_points, alphamin, alphamax, align_corners, out);                  \
+        else                                                                                       \
+            hipLaunchKernelGGL((trilinear_fwd_kernel<R, NN, unsigned>), grid, block, 0, st, p,     \
+                               n_points, alphamin, alphamax, align_corners, out);                  \
+    } while (0)
     if (sum && !mode_nearest) LAUNCH(REDUCE_SUM, false);
     else if (sum) LAUNCH(REDUCE_SUM, true);
     else if (!mode_nearest) LAUNCH(REDUCE_MAX, false);
@@ -324,7 +333,9 @@ int ddrr_trilinear_forward_channels(const float *volume, const unsigned char *la
                                     const float *alphamin, const float *alphamax,
                                     int align_corners, int det_h, int det_w, int tile_h,
                                     int tile_w, float *out, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_trilinear_forward_channels (mask_to_channels)"))
+        return rc;
     if (!labels || !out || C < 1) return fail(-1, "null labels/out or C < 1");
     if (!alphamin || !alphamax) return fail(-1, "null alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
@@ -346,7 +357,7 @@ int ddrr_trilinear_backward(const float *volume, int dx, int dy, int dz, const f
                             int mode_nearest, int align_corners, int det_h, int det_w, int tile_h,
                             int tile_w, float *g_source, float *g_target, float *g_img,
                             float *g_alpha, float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N, nullptr)) return rc;
     if (!grad_out || !alphamin || !alphamax) return fail(-1, "null grad_out / alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (B == 0 || N == 0) return 0;
@@ -354,10 +365,18 @@ int ddrr_trilinear_backward(const float *volume, int dx, int dy, int dz, const f
                                 eps, det_h, det_w, tile_h, tile_w);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(grid_for(p)), block(kBlock);
-#define LAUNCH(NN, WV)                                                                          \
-    hipLaunchKernelGGL((trilinear_bwd_kernel<NN, WV>), grid, block, 0, st, p, grad_out, n_points, \
-                       alphamin, alphamax, align_corners, g_source, g_target, g_img, g_alpha,     \
-                       g_volume)
+    const bool wide = wide_offsets(dx, dy, dz);
+#define LAUNCH(NN, WV)                                                                             \
+    do {                                                                                           \
+        if (wide)                                                                                  \
+            hipLaunchKernelGGL((trilinear_bwd_kernel<NN, WV, Off64>), grid, block, 0, st, p,       \
+                               grad_out, n_points, alphamin, alphamax, align_corners, g_source,    \
+                               g_target, g_img, g_alpha, g_volume);                                \
+        else                                                                                       \
+            hipLaunchKernelGGL((trilinear_bwd_kernel<NN, WV, unsigned>), grid, block, 0, st, p,    \
+                               grad_out, n_points, alphamin, alphamax, align_corners, g_source,    \
+                               g_target, g_img, g_alpha, g_volume);                                \
+    } while (0)
     if (mode_nearest && g_volume) LAUNCH(true, true);
     else if (mode_nearest) LAUNCH(true, false);
     else if (g_volume) LAUNCH(false, true);
@@ -375,7 +394,9 @@ int ddrr_trilinear_backward_channels(const float *volume, const unsigned char *l
                                      int align_corners, int det_h, int det_w, int tile_h,
                                      int tile_w, float *g_source, float *g_target, float *g_img,
                                      float *g_alpha, float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_trilinear_backward_channels (mask_to_channels)"))
+        return rc;
     if (!labels || !grad_out || !alphamin || !alphamax || C < 1)
         return fail(-1, "null labels / grad_out / alphamin / alphamax or C < 1");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
@@ -400,7 +421,9 @@ int ddrr_trilinear_samples(const float *volume, int dx, int dy, int dz, const fl
                            float voxel_shift, float eps, int n_points, const float *alphamin,
                            const float *alphamax, int mode_nearest, int align_corners,
                            float *samples, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_trilinear_samples (callable reducefn)"))
+        return rc;
     if (!samples || !alphamin || !alphamax) return fail(-1, "null samples / alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (B == 0 || N == 0) return 0;
@@ -425,7 +448,9 @@ int ddrr_trilinear_samples_backward(const float *volume, int dx, int dy, int dz,
                                     int mode_nearest, int align_corners, float *g_source,
                                     float *g_target, float *g_img, float *g_alpha,
                                     float *g_volume, void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N,
+                              "ddrr_trilinear_samples_backward (callable reducefn)"))
+        return rc;
     if (!grad_samples || !alphamin || !alphamax)
         return fail(-1, "null grad_samples / alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
@@ -453,7 +478,7 @@ int ddrr_trilinear_backward_max(const float *volume, int dx, int dy, int dz, con
                                 int mode_nearest, int align_corners, float *g_source,
                                 float *g_target, float *g_img, float *g_alpha, float *g_volume,
                                 void *stream) {
-    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N)) return rc;
+    if (int rc = check_common(volume, dx, dy, dz, source, src_n, target, B, N, nullptr)) return rc;
     if (!grad_out || !alphamin || !alphamax) return fail(-1, "null grad_out / alphamin / alphamax");
     if (n_points < 2) return fail(-1, "n_points must be >= 2");
     if (B == 0 || N == 0) return 0;
@@ -461,10 +486,18 @@ int ddrr_trilinear_backward_max(const float *volume, int dx, int dy, int dz, con
                                 eps, 0, 0, 1, 64);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(grid_for(p)), block(kBlock);
-#define LAUNCH(NN, WV)                                                                           \
-    hipLaunchKernelGGL((trilinear_bwd_max_kernel<NN, WV>), grid, block, 0, st, p, grad_out,       \
-                       n_points, alphamin, alphamax, align_corners, g_source, g_target, g_img,    \
-                       g_alpha, g_volume)
+    const bool wide = wide_offsets(dx, dy, dz);
+#define LAUNCH(NN, WV)                                                                             \
+    do {                                                                                           \
+        if (wide)                                                                                  \
+            hipLaunchKernelGGL((trilinear_bwd_max_kernel<NN, WV, Off64>), grid, block, 0, st, p,   \
+                               grad_out, n_points, alphamin, alphamax, align_corners, g_source,    \
+                               g_target, g_img, g_alpha, g_volume);                                \
+        else                                                                                       \
+            hipLaunchKernelGGL((trilinear_bwd_max_kernel<NN, WV, unsigned>), grid, block, 0, st,   \
+                               p, grad_out, n_points, alphamin, alphamax, align_corners, g_source, \
+                               g_target, g_img, g_alpha, g_volume);                                \
+    } while (0)
     if (mode_nearest && g_volume) LAUNCH(true, true);
     else if (mode_nearest) LAUNCH(true, false);
     else if (g_volume) LAUNCH(false, true);

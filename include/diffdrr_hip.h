@@ -37,7 +37,12 @@
  *    be initialised).  Calls that may run concurrently -- other streams, a
  *    captured graph next to eager launches -- must be given different buffers;
  *  - return value: 0 on success, otherwise a hipError_t (or -1 for an
- *    argument error); ddrr_last_error() describes the last failure.
+ *    argument error); ddrr_last_error() describes the last failure;
+ *  - volume size: any volume of at most 2^30 voxels.  Above that, up to 2^34 voxels
+ *    with every dim < 2^16 and dy * dz <= 2^28, the Siddon and marcher entries with
+ *    and without bricks take it (per-ray kernels with 64-bit voxel offsets); the
+ *    mask_to_channels, callable-reducefn (segments / samples), float64 and general
+ *    entries stay at 2^30 and return an error naming themselves and that cap.
  *
  * det_h/det_w/tile_h/tile_w are a pure performance hint: when the N rays of a
  * pose are a row-major det_h x det_w detector grid (detector.py:126) each
