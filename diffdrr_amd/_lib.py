@@ -6,160 +6,141 @@ runtime torch already has in the process (same ``libamdhip64.so.7`` soname):
 kernels can then be launched on torch's current stream with torch's device
 pointers.  There is deliberately no CPU or pure-PyTorch fallback: if the
 library is missing, rendering raises.
+
+The headers are the only place the binding's types are written down: every entry's ctypes argument
+and result types, and the ``DDRR_*`` constants Python uses, are read from them when this module is
+imported (:func:`parse_header`).  A declaration the parser cannot map exactly is an error, never a
+guess.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_double, c_float, c_int, c_long, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_void_p
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_hip.so")
+# The ABI versions ops.py is written against: the header's DDRR_*ABI_VERSION and the loaded library's
+# own must both be these (checked on import and on load).
 ABI_VERSION = 33
-BRICKS_CLEARED = 2  # include/diffdrr_hip.h DDRR_BRICKS_CLEARED (a bit of ranges_valid)
-
-REDUCE_SUM, REDUCE_MAX = 0, 1
-LOOKUP_STEP, LOOKUP_MID_NEAREST, LOOKUP_MID_TRILINEAR = 0, 1, 2
-SIDDON_AUX = 8
-AUX_INTERLEAVED, AUX_BLOCKED, AUX_PACKED = 0, 1, 2
-REC_BLOCK_RAYS, REC_BLOCK_FLOATS = 16, 80  # blocked float record (csrc/record_layout.h)
-BRICKS_F32, BRICKS_Q16, BRICKS_Q16_PACKED = 0, 1, 2  # how a brick is held in LDS (ddrr_siddon_forward_bricks)
-PACKED_AUX_PLANES = 7  # fixed-point record (csrc/record_pack.h)
+MI_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
+_ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
+_RESTYPES_OF = {"int": c_int, "long": c_long, "const char *": c_char_p}
+_DECLARATION = re.compile(r"(.*?)\b(ddrr_\w+)\s*\((.*)\)", re.S)
+_POINTER = re.compile(r"[\w\s]+\*[\s*]*\w+")   # T *name, const T *name, T **name
+_SCALAR = re.compile(r"(\w+)\s+\w+")            # T name
 
-# name -> argtypes, in the order of include/diffdrr_hip.h
-_SIGNATURES = {
-    "ddrr_siddon_forward": [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _F, _F, _I, _I, _I, _I, _I,
-                            _I, _I, _P, _P, _P, _P],
-    "ddrr_siddon_forward_bricks": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _F, _I,
-                                   _P, _I, _P, _P],
-    "ddrr_siddon_forward_bricks_masked": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _F, _I,
-                                          _P, _I, _P, _P, _P],
-    "ddrr_siddon_backward_rays": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P],
-    "ddrr_siddon_backward_volume": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _I,
-                                    _I, _I, _I, _P, _P],
-    "ddrr_siddon_forward_channels": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _F, _F, _I,
-                                     _I, _I, _I, _P, _P],
-    "ddrr_siddon_forward_channels_bricks": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F,
-                                            _P, _P, _P],
-    "ddrr_channel_words": [_P, _P, _L, _I, _P, _P, _I, _P],
-    "ddrr_siddon_forward_channels_bricks_words": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F,
-                                                  _P, _P, _P],
-    "ddrr_siddon_backward_channels_bricks": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F,
-                                             _P, _P, _P],
-    "ddrr_siddon_backward_channels_volume_bricks": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F,
-                                                    _F, _P, _P, _P],
-    "ddrr_trilinear_backward_channels_volume_bricks": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I,
-                                                       _F, _F, _I, _P, _P, _P, _P, _P],
-    "ddrr_trilinear_backward_channels_bricks": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F,
-                                                _F, _I, _P, _P, _P, _P, _P],
-    "ddrr_trilinear_alpha_range": [_P, _I, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P],
-    "ddrr_trilinear_backward_max": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P, _P,
-                                    _I, _I, _P, _P, _P, _P, _P, _P],
-    "ddrr_trilinear_samples": [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _F, _F, _I, _P, _P, _I, _I,
-                               _P, _P],
-    "ddrr_trilinear_samples_backward": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P,
-                                        _P, _I, _I, _P, _P, _P, _P, _P, _P],
-    "ddrr_siddon_backward_midpoint": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _I,
-                                      _P, _P, _P, _P, _P],
-    "ddrr_siddon_segments": [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _F, _F, _P, _P],
-    "ddrr_siddon_segments_backward": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _P, _P,
-                                      _P, _P, _P],
-    "ddrr_siddon_backward_channels": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F,
-                                      _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "ddrr_trilinear_backward_channels": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F,
-                                         _F, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P,
-                                         _P],
-    "ddrr_trilinear_forward": [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _F, _F, _I, _P, _P, _I,
-                               _I, _I, _I, _I, _I, _I, _P, _P],
-    "ddrr_trilinear_backward": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P, _P,
-                                _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "ddrr_siddon_backward_volume_bricks": [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P,
-                                           _P],
-    "ddrr_trilinear_forward_channels": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _F, _F, _I,
-                                        _P, _P, _I, _I, _I, _I, _I, _P, _P],
-    "ddrr_trilinear_forward_bricks": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P,
-                                      _P, _P, _P, _P],
-    "ddrr_trilinear_backward_rays": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P,
-                                     _P],
-    "ddrr_trilinear_backward_volume_bricks": [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I,
-                                              _P, _P, _P, _P, _P],
-    "ddrr_pose_euler_forward": [_P, _P, _I, _I, _I, _P, _I, _P, _P],
-    "ddrr_pose_euler_backward": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P],
-    "ddrr_siddon_ncc_workspace_bytes": [_I],
-    "ddrr_pose_raygen_forward": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P, _P],
-    "ddrr_siddon_ncc_forward": [_P, _P, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P, _P],
-    "ddrr_siddon_ncc_backward_pose": [_P, _P, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I,
-                                      _P, _I, _I, _F, _I, _P, _P, _P, _P],
-    "ddrr_siddon_backward_pose_euler": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _F, _I, _P,
-                                        _P, _P, _P],
-    "ddrr_pose_adam_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P],
-    "ddrr_ncc_forward": [_P, _L, _P, _I, _I, _F, _P, _P, _P],
-    "ddrr_ncc_backward": [_P, _L, _P, _P, _P, _I, _I, _I, _P, _P, _P],
-    "ddrr_ncc_patch_forward": [_P, _L, _P, _I, _I, _I, _I, _F, _P, _P, _P],
-    "ddrr_ncc_patch_backward": [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
-    "ddrr_sobel_forward": [_P, _I, _I, _I, _P, _P],
-    "ddrr_sobel_backward": [_P, _I, _I, _I, _P, _P],
-    "ddrr_blur_sobel_forward": [_P, _L, _I, _I, _I, _P, _I, _P, _P],
-    "ddrr_blur_sobel_backward": [_P, _I, _I, _I, _P, _I, _P, _P],
-    "ddrr_raygen_forward": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "ddrr_siddon_backward_pose": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P],
-    "ddrr_siddon_forward_f64": [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _D, _D, _I, _P, _P, _P],
-    "ddrr_siddon_backward_f64": [_I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _D, _D, _P, _P, _P,
-                                 _P, _P],
-    "ddrr_trilinear_forward_f64": [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _D, _D, _I, _P, _P, _P,
-                                   _P],
-    "ddrr_trilinear_backward_f64": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _D, _D, _I, _P, _P,
-                                    _P, _P, _P, _P, _P, _P],
-    "ddrr_siddon_segments_general": [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _D, _D, _I, _I, _I,
-                                     _P, _P],
-    "ddrr_siddon_segments_general_backward": [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _D,
-                                              _D, _I, _I, _I, _P, _P, _P, _P, _P],
-    "ddrr_trilinear_samples_general": [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _D, _D, _I, _P,
-                                       _P, _I, _I, _I, _P, _P],
-    "ddrr_trilinear_samples_general_backward": [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _D,
-                                                _D, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
-    "ddrr_channel_words_state_bytes": [],
-    "ddrr_brick_workspace_bytes": [_I, _I, _I, _I],
-    "ddrr_brick_launch_workspace_bytes": [_I, _I, _I],
-    "ddrr_trilinear_forward_channels_bricks": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F,
-                                               _I, _P, _P, _P, _P, _P],
-}
-# (entries that return a size, not a status)
-_RESTYPES = {"ddrr_brick_workspace_bytes": c_long, "ddrr_brick_launch_workspace_bytes": c_long,
-             "ddrr_siddon_ncc_workspace_bytes": c_long, "ddrr_channel_words_state_bytes": c_long}
-EXPORTS = ["ddrr_abi_version", "ddrr_last_error", *_SIGNATURES]
+
+def parse_header(text: str):
+    """The entries of a C header -- every declaration ``int|long|const char * ddrr_...(...);`` -- and its
+    integer ``#define DDRR_*`` constants.  Any pointer is ``c_void_p``; ``int``, ``long``, ``float`` and
+    ``double`` map to their ctypes; a return type other than ``int``, ``long`` or ``const char *``, any
+    other parameter type (``unsigned``, ``size_t``, ``bool``, a function pointer) or a declaration that
+    does not read as one raises ValueError naming the entry.
+    -> (name -> argtypes, name -> restype, DDRR_NAME -> int), entries in the header's order"""
+    code = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    code = re.sub(r"//[^\n]*", "", code)
+    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(DDRR_\w+)[ \t]+(\d+)[ \t]*$",
+                                                code, re.M)}
+    code = re.sub(r"^[ \t]*#[^\n]*", "", code, flags=re.M)
+    signatures, restypes = {}, {}
+    for stmt in re.split(r"[;{}]", code):
+        if not re.search(r"\bddrr_\w+\s*\(", stmt):
+            continue
+        m = _DECLARATION.fullmatch(" ".join(stmt.split()))
+        name = m.group(2) if m else re.search(r"\bddrr_\w+", stmt).group(0)
+        ret = re.sub(r"\s*\*\s*", " *", m.group(1)).strip() if m else None
+        if ret not in _RESTYPES_OF:
+            raise ValueError(f"{name}: cannot bind the declaration {' '.join(stmt.split())!r} "
+                             "(return type int, long or const char * expected)")
+        params = m.group(3).strip()
+        argtypes = []
+        for param in ([] if params == "void" else params.split(",")):
+            param = param.strip()
+            scalar = _SCALAR.fullmatch(param)
+            if _POINTER.fullmatch(param):
+                argtypes.append(c_void_p)
+            elif scalar and scalar.group(1) in _ARGTYPES:
+                argtypes.append(_ARGTYPES[scalar.group(1)])
+            else:
+                raise ValueError(f"{name}: cannot bind the parameter {param!r} (a pointer, int, long, float "
+                                 "or double expected)")
+        if name in signatures:
+            raise ValueError(f"{name}: declared twice")
+        signatures[name], restypes[name] = argtypes, _RESTYPES_OF[ret]
+    return signatures, restypes, defines
+
+
+class Header(NamedTuple):
+    """The C ABI one header declares, as the binding uses it."""
+    path: str
+    prefix: str         # of the entries every such library has: <prefix>_abi_version, <prefix>_last_error
+    version: int        # the ABI version the Python side is written against
+    argtypes: dict      # every entry -> ctypes argument types
+    restypes: dict      # every entry -> ctypes result type
+    defines: dict       # DDRR_* -> int
+
+    @classmethod
+    def read(cls, name: str, prefix: str, version: int) -> "Header":
+        path = os.path.join(_INCLUDE, name)
+        with open(path) as f:
+            argtypes, restypes, defines = parse_header(f.read())
+        macro = f"{prefix.upper()}_ABI_VERSION"
+        if defines.get(macro) != version:
+            raise RuntimeError(f"{path}: {macro} is {defines.get(macro)}, the binding is written against {version}")
+        return cls(path, prefix, version, argtypes, restypes, defines)
+
+    def tables(self):
+        """-> (signatures, restypes, exports): the status- and size-returning entries (all but
+        <prefix>_abi_version and <prefix>_last_error) -> argtypes, those of them that return a size
+        -> restype, every entry's name"""
+        own = (f"{self.prefix}_abi_version", f"{self.prefix}_last_error")
+        signatures = {n: a for n, a in self.argtypes.items() if n not in own}
+        return signatures, {n: self.restypes[n] for n in signatures if self.restypes[n] is not c_int}, \
+            list(self.argtypes)
+
+    def constants(self, *names):
+        return [self.defines[f"{self.prefix.upper()}_{n}"] for n in names]
+
+
+HEADER = Header.read("diffdrr_hip.h", "ddrr", ABI_VERSION)
+_SIGNATURES, _RESTYPES, EXPORTS = HEADER.tables()
+
+REDUCE_SUM, REDUCE_MAX = HEADER.constants("REDUCE_SUM", "REDUCE_MAX")
+LOOKUP_STEP, LOOKUP_MID_NEAREST, LOOKUP_MID_TRILINEAR = HEADER.constants(
+    "LOOKUP_STEP", "LOOKUP_MID_NEAREST", "LOOKUP_MID_TRILINEAR")
+SIDDON_AUX, = HEADER.constants("SIDDON_AUX")
+AUX_INTERLEAVED, AUX_BLOCKED, AUX_PACKED = HEADER.constants("AUX_INTERLEAVED", "AUX_BLOCKED", "AUX_PACKED")
+REC_BLOCK_RAYS, REC_BLOCK_FLOATS = HEADER.constants("REC_BLOCK_RAYS", "REC_BLOCK_FLOATS")  # csrc/record_layout.h
+# how a brick is held in LDS (ddrr_siddon_forward_bricks); BRICKS_CLEARED is a bit of ranges_valid
+BRICKS_F32, BRICKS_Q16, BRICKS_Q16_PACKED, BRICKS_CLEARED = HEADER.constants(
+    "BRICKS_F32", "BRICKS_Q16", "BRICKS_Q16_PACKED", "BRICKS_CLEARED")
+PACKED_AUX_PLANES, TRI_AUX_PLANES = HEADER.constants("PACKED_AUX_PLANES", "TRI_AUX_PLANES")
 
 
 class DdrrLibrary:
-    """A loaded implementation of the C ABI (the HIP product library; the
-    tests also bind their host emulation build through this class).  The
-    MutualInformation library (include/diffdrr_mi_hip.h) is bound by the same
-    class with its own tables (:func:`mi_library`)."""
+    """A loaded implementation of the C ABI of ``header`` (the HIP product library; the tests also bind
+    their host emulation build through this class; :func:`mi_library` binds the MutualInformation
+    library, include/diffdrr_mi_hip.h).  Checks that every entry of the header is exported and that the
+    library's ABI version is the binding's."""
 
-    def __init__(self, path: str, exports=None, signatures=None, restypes=None, abi_version=None,
-                 prefix: str = "ddrr"):
-        exports = EXPORTS if exports is None else exports
-        signatures = _SIGNATURES if signatures is None else signatures
-        restypes = _RESTYPES if restypes is None else restypes
-        abi_version = ABI_VERSION if abi_version is None else abi_version
+    def __init__(self, path: str, header: Header = HEADER):
         self.path = path
         self.cdll = ctypes.CDLL(path)
-        for name in exports:
+        for name in header.argtypes:
             if not hasattr(self.cdll, name):
                 raise RuntimeError(f"{path} does not export {name}")
-        version = getattr(self.cdll, f"{prefix}_abi_version")
-        version.restype = c_int
-        self._last_error = getattr(self.cdll, f"{prefix}_last_error")
-        self._last_error.restype = ctypes.c_char_p
-        got = version()
-        if got != abi_version:
-            raise RuntimeError(f"{path}: ABI version {got}, expected {abi_version}")
-        for name, argtypes in signatures.items():
             fn = getattr(self.cdll, name)
-            fn.argtypes = argtypes
-            fn.restype = restypes.get(name, c_int)
+            fn.argtypes, fn.restype = header.argtypes[name], header.restypes[name]
+        got = getattr(self.cdll, f"{header.prefix}_abi_version")()
+        if got != header.version:
+            raise RuntimeError(f"{path}: ABI version {got}, expected {header.version}")
+        self._last_error = getattr(self.cdll, f"{header.prefix}_last_error")
 
     def query(self, name: str, *args):
         """An entry that returns a value (``_RESTYPES``), not a status."""
@@ -194,22 +175,14 @@ def get_lib() -> DdrrLibrary:
 # ----------------------------------------------------------------- libdiffdrr_mi_hip.so
 # MutualInformation (C ABI: include/diffdrr_mi_hip.h): a library of its own, with its own version
 MI_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_mi_hip.so")
-MI_ABI_VERSION = 1
-MI_MAX_BINS = 256
-
-_MI_SIGNATURES = {
-    "ddrr_mi_workspace_bytes": [_I, _I, _I, _I],
-    "ddrr_mi_state_floats": [_I],
-    "ddrr_mi_forward": [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _F, _I, _P, _L, _P, _P, _P],
-    "ddrr_mi_backward": [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P],
-}
-_MI_RESTYPES = {"ddrr_mi_workspace_bytes": c_long, "ddrr_mi_state_floats": c_long}
-MI_EXPORTS = ["ddrr_mi_abi_version", "ddrr_mi_last_error", *_MI_SIGNATURES]
+MI_HEADER = Header.read("diffdrr_mi_hip.h", "ddrr_mi", MI_ABI_VERSION)
+_MI_SIGNATURES, _MI_RESTYPES, MI_EXPORTS = MI_HEADER.tables()
+MI_MAX_BINS, = MI_HEADER.constants("MAX_BINS")
 
 
 def mi_library(path: str) -> DdrrLibrary:
     """Load and check a build of include/diffdrr_mi_hip.h."""
-    return DdrrLibrary(path, MI_EXPORTS, _MI_SIGNATURES, _MI_RESTYPES, MI_ABI_VERSION, prefix="ddrr_mi")
+    return DdrrLibrary(path, MI_HEADER)
 
 
 _mi_lib: DdrrLibrary | None = None

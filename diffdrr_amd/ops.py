@@ -13,7 +13,7 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import REDUCE_MAX, REDUCE_SUM, SIDDON_AUX
+from ._lib import REDUCE_MAX, REDUCE_SUM, SIDDON_AUX, TRI_AUX_PLANES
 
 _REDUCE = {"sum": REDUCE_SUM, "max": REDUCE_MAX}
 _LOOKUP = {"step": _lib.LOOKUP_STEP, "mid_nearest": _lib.LOOKUP_MID_NEAREST,
@@ -66,13 +66,18 @@ def _launch(name, device, *args):
     device switch only where the current device is another one: `torch.cuda.device(...)` +
     `torch.cuda.current_stream()` cost ~10 us of host time per call -- a third of what an eager
     registration iteration's six launches spend on the host, tools/eager_registration_loop.py.)"""
+    _launch_on(_lib.get_lib(), name, device, args)
+
+
+def _launch_on(lib, name, device, args):
+    """:func:`_launch` through the loaded library `lib` (the MutualInformation kernels have their own)."""
     index = device.index
     current = torch.cuda.current_device()
     if index is None or index == current:
-        _lib.get_lib().call(name, *args, torch._C._cuda_getCurrentRawStream(current))
+        lib.call(name, *args, torch._C._cuda_getCurrentRawStream(current))
         return
     with torch.cuda.device(index):
-        _lib.get_lib().call(name, *args, torch._C._cuda_getCurrentRawStream(index))
+        lib.call(name, *args, torch._C._cuda_getCurrentRawStream(index))
 
 
 def _query(name, *args):
@@ -111,6 +116,100 @@ def _check_rays(volume, source, target, img, dtype=torch.float32):
     if img is not None and img.numel() != B * N:
         raise ValueError(f"img must have B*N = {B * N} elements, got {tuple(img.shape)}")
     return B, N
+
+
+class _Rays:
+    """The rays of one launch as contiguous tensors -- the caller's own where they are contiguous,
+    copies where not -- and, through :meth:`ptr`, every further tensor the launch reads.  Each copy stays
+    referenced with the batch until the launch has been enqueued: the autograd nodes hand back the ray
+    tensors they were given (a chunk of a (B, N, 3) target is a strided view), and a copy freed before
+    its launch is memory that the next allocation may take and overwrite first.  Unchecked (the callers
+    of the entries without a volume check what they need); :func:`_rays` checks them first."""
+    __slots__ = ("B", "N", "source", "target", "img", "_held")
+
+    def __init__(self, source, target, img):
+        self.B, self.N, _ = target.shape
+        self.source, self.target = source.contiguous(), target.contiguous()
+        self.img = None if img is None else img.contiguous()
+        self._held = []
+
+    def ptr(self, t):
+        """The device pointer of `t` made contiguous (None for None), held with the batch."""
+        if t is None:
+            return None
+        t = t.contiguous()
+        self._held.append(t)
+        return t.data_ptr()
+
+    def vol(self, volume):
+        """The ABI's (volume, dx, dy, dz) run."""
+        return (self.ptr(volume), *volume.shape)
+
+    def rays(self):
+        """The ABI's (source, src_n, target, img) run of the per-ray entries."""
+        return self.source.data_ptr(), self.source.shape[1], self.target.data_ptr(), _ptr(self.img)
+
+    def grid(self):
+        """The (source, target, img) run of the brick entries (one source per pose: no src_n)."""
+        return self.source.data_ptr(), self.target.data_ptr(), _ptr(self.img)
+
+
+def _rays(volume, source, target, img, dtype=torch.float32) -> _Rays:
+    """:func:`_check_rays`, then the batch."""
+    _check_rays(volume, source, target, img, dtype)
+    return _Rays(source, target, img)
+
+
+def _grid(det, N, source):
+    """(det_h, det_w) of a brick launch, whose rays must be one source per pose and an H x W >= 2 x 2
+    detector grid."""
+    H, W = int(det[0]), int(det[1])
+    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
+        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
+    return H, W
+
+
+def _channels(grad_out, B, N):
+    """C of a channel render's gradient grad_out (B, C, N)."""
+    C = grad_out.shape[1]
+    if grad_out.shape != (B, C, N):
+        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
+    return C
+
+
+def _check_labels(labels_u8, volume=None):
+    """A uint8 label map of the volume's shape (any 3-D one for the entries that take no volume)."""
+    if volume is None:
+        if labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3:
+            raise ValueError("labels must be a 3-D uint8 tensor")
+    elif labels_u8.dtype != torch.uint8 or labels_u8.shape != volume.shape:
+        raise ValueError("labels must be a uint8 tensor of the volume's shape")
+
+
+def _grad_buffers(B, N, dtype, device, *, rays, img, alpha=None, volume_shape=None, new=torch.empty):
+    """The outputs of a backward entry, in the ABI's order, None where not asked: g_source and g_target
+    (B, N, 3) per ray with `rays`, g_img (B, N) with `img`, g_alpha (B, N, 2) with `alpha` (the Siddon
+    entries have none: alpha=None leaves the key out), g_volume zero-filled (the kernels accumulate into
+    it) where a `volume_shape` is given.  `new`: torch.empty, or torch.zeros for kernels that accumulate
+    the per-ray outputs too."""
+    def buf(want, *shape):
+        return new(*shape, dtype=dtype, device=device) if want else None
+
+    g = {"g_source": buf(rays, B, N, 3), "g_target": buf(rays, B, N, 3), "g_img": buf(img, B, N)}
+    if alpha is not None:
+        g["g_alpha"] = buf(alpha, B, N, 2)
+    g["g_volume"] = None if volume_shape is None else \
+        torch.zeros(tuple(volume_shape), dtype=dtype, device=device)
+    return g
+
+
+def _batch_grad(g_out, B):
+    """(g_out, g_stride) of the gradient of B per-pose values: (B) values with stride 1, or one value for
+    the whole batch with stride 0, read in place (the gradient of a summed objective: a 0-dim tensor, or
+    what autograd expands it to)."""
+    if g_out.dim() == 0 or (g_out.dim() == 1 and B > 1 and g_out.stride(0) == 0):
+        return g_out, 0
+    return g_out.contiguous(), 1
 
 
 def _empty(B, N):
@@ -154,20 +253,18 @@ def siddon_forward(volume, source, target, img, *, voxel_shift=0.5, eps=1e-8, re
                    lookup="step", align_corners=False, want_aux=False, count_voxels=False,
                    det=None, tile=None):
     """-> (out (B,N), aux (B,N,8) | None, n_vox (B,N) int32 | None)"""
-    B, N = _check_rays(volume, source, target, img)
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
     out = torch.empty(B, N, dtype=torch.float32, device=volume.device)
     aux = torch.empty(B, N, SIDDON_AUX, dtype=torch.float32, device=volume.device) \
         if want_aux else None
     nvox = torch.empty(B, N, dtype=torch.int32, device=volume.device) if count_voxels else None
-    dh, dw, th, tw = _hints(det, tile, N)
+    hints = _hints(det, tile, N)
     if _empty(B, N):
         return out, aux, nvox
     _launch(
-        "ddrr_siddon_forward", volume.device, volume.data_ptr(), *volume.shape, source.data_ptr(),
-        source.shape[1], target.data_ptr(), _ptr(img), B, N, float(voxel_shift), float(eps),
-        reduce_code(reducefn), _LOOKUP[lookup], int(bool(align_corners)), dh, dw, th, tw,
+        "ddrr_siddon_forward", volume.device, *r.vol(volume), *r.rays(), B, N, float(voxel_shift), float(eps),
+        reduce_code(reducefn), _LOOKUP[lookup], int(bool(align_corners)), *hints,
         out.data_ptr(), _ptr(aux), _ptr(nvox))
     return out, aux, nvox
 
@@ -375,14 +472,11 @@ def siddon_forward_bricks(volume, source, target, img, det, *, voxel_shift=0.5, 
     clears nothing.  ``pixel_mask``: an int32 tensor of ceil(N / 32) words, one bit per pixel of the
     grid (:func:`pixel_mask_of`): only the pixels whose bit is set are rendered, image and record
     hold zeros at the others (``p_subsample``: reference drr.py:36-39, 142-147)."""
-    B, N = _check_rays(volume, source, target, img)
-    H, W = int(det[0]), int(det[1])
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    H, W = _grid(det, N, source)
     if storage != "f32" and not brick_storage_applies(volume):
         storage = "f32"
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
     # (want_image = False with want_aux: the record alone -- siddon_ncc_forward forms the image)
     need_out = want_image or not want_aux
     if out is not None and (not need_out or out.shape != (B, N) or out.dtype != torch.float32
@@ -410,8 +504,7 @@ def siddon_forward_bricks(volume, source, target, img, det, *, voxel_shift=0.5, 
         raise ValueError("pixel_mask: a contiguous int32 tensor of ceil(N / 32) words on the volume's device")
     _launch(
         "ddrr_siddon_forward_bricks" if pixel_mask is None else "ddrr_siddon_forward_bricks_masked",
-        volume.device, volume.data_ptr(), *volume.shape,
-        source.data_ptr(), target.data_ptr(), _ptr(img), B, H, W, float(voxel_shift), float(eps),
+        volume.device, *r.vol(volume), *r.grid(), B, H, W, float(voxel_shift), float(eps),
         _ptr(out), _ptr(aux), float(record_vmax) if packed else 0.0,
         _BRICK_STORAGE[storage], _ptr(ranges), int(valid) | (_lib.BRICKS_CLEARED if cleared else 0),
         launch_ws.data_ptr(), *(() if pixel_mask is None else (pixel_mask.data_ptr(),)))
@@ -437,20 +530,14 @@ def siddon_backward_rays(aux, grad_out, source, target, img, *, eps=1e-8, reduce
     the brick forward.  -> (g_source (B,N,3) per ray, g_target (B,N,3), g_img (B,N) | None)"""
     B, N, _ = target.shape
     layout = _aux_layout(aux, B, N)
-    grad_out = grad_out.contiguous()
     g_source = torch.empty(B, N, 3, dtype=torch.float32, device=target.device)
     g_target = torch.empty(B, N, 3, dtype=torch.float32, device=target.device)
     g_img = torch.empty(B, N, dtype=torch.float32, device=target.device) if want_img_grad else None
-    if _empty(B, N):
-        return g_source, g_target, g_img
-    # (named, so that a contiguous copy outlives the launch: the autograd nodes hand back the ray
-    # tensors they were given -- a chunk of a (B, N, 3) target is a strided view)
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    _launch(
-        "ddrr_siddon_backward_rays", target.device, aux.data_ptr(), layout, grad_out.data_ptr(), source.data_ptr(),
-        source.shape[1], target.data_ptr(), _ptr(img), B, N, float(eps),
-        reduce_code(reducefn), g_source.data_ptr(), g_target.data_ptr(), _ptr(g_img))
+    if not _empty(B, N):
+        r = _Rays(source, target, img)
+        _launch(
+            "ddrr_siddon_backward_rays", target.device, aux.data_ptr(), layout, r.ptr(grad_out), *r.rays(), B, N,
+            float(eps), reduce_code(reducefn), g_source.data_ptr(), g_target.data_ptr(), _ptr(g_img))
     return g_source, g_target, g_img
 
 
@@ -496,11 +583,7 @@ def ncc_backward(x1, x2, stats, g_out, want_x1, want_x2):
     shared = x1.shape[0] == 1 and B != 1
     x1, x2 = x1.contiguous(), x2.contiguous()
     # (the gradient of `.sum()` / `.mean()` arrives as an expanded scalar: read in place, stride 0)
-    # (one value for the whole batch: the gradient of a summed objective -- a 0-dim tensor, or what
-    # autograd expands it to)
-    g_stride = 0 if (g_out.dim() == 0 or (g_out.dim() == 1 and B > 1 and g_out.stride(0) == 0)) else 1
-    if g_stride:
-        g_out = g_out.contiguous()
+    g_out, g_stride = _batch_grad(g_out, B)
     g_x2 = torch.empty_like(x2) if want_x2 else None
     g_x1 = torch.empty_like(x2) if (want_x1 and not shared) else None
     if B:
@@ -530,9 +613,7 @@ def ncc_patch_backward(x1, x2, coef, g_out, p):
     B, H, W = x2.shape
     shared = x1.shape[0] == 1 and B != 1
     x1, x2 = x1.contiguous(), x2.contiguous()
-    g_stride = 0 if (g_out.dim() == 0 or (g_out.dim() == 1 and B > 1 and g_out.stride(0) == 0)) else 1
-    if g_stride:
-        g_out = g_out.contiguous()
+    g_out, g_stride = _batch_grad(g_out, B)
     g_x2 = torch.empty_like(x2)
     if B:
         _launch("ddrr_ncc_patch_backward", x2.device, x1.data_ptr(), 0 if shared else H * W, x2.data_ptr(),
@@ -721,11 +802,7 @@ def siddon_ncc_backward_pose(aux, img, x1, stats, g_out, source, target, Mw, Ain
     pose_euler_backward in one launch."""
     B, N = img.shape
     shared = x1.shape[0] == 1 and B != 1
-    # (one value for the whole batch: the gradient of a summed objective -- a 0-dim tensor, or what
-    # autograd expands it to)
-    g_stride = 0 if (g_out.dim() == 0 or (g_out.dim() == 1 and B > 1 and g_out.stride(0) == 0)) else 1
-    if g_stride:
-        g_out = g_out.contiguous()
+    g_out, g_stride = _batch_grad(g_out, B)
     x1, img, source, target = (t.contiguous() for t in (x1, img, source, target))
     Mw, Ainv, P, rot, xyz, reorient34 = (t.contiguous() for t in (Mw, Ainv, P, rot, xyz, reorient34))
     dev = img.device
@@ -761,18 +838,15 @@ def siddon_backward_pose_euler(aux, grad_out, source, Mw, Ainv, P, rot, xyz, axe
 
 def siddon_backward_volume(volume, source, target, img, grad_out, *, voxel_shift=0.5, eps=1e-8,
                            reducefn="sum", det=None, tile=None):
-    B, N = _check_rays(volume, source, target, img)
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
     g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format)
-    dh, dw, th, tw = _hints(det, tile, N)
+    hints = _hints(det, tile, N)
     if _empty(B, N):
         return g_volume
-    volume, source, target, grad_out = (t.contiguous() for t in (volume, source, target, grad_out))
-    img = None if img is None else img.contiguous()
     _launch(
-        "ddrr_siddon_backward_volume", volume.device, volume.data_ptr(), *volume.shape, source.data_ptr(),
-        source.shape[1], target.data_ptr(), _ptr(img), grad_out.data_ptr(), B, N,
-        float(voxel_shift), float(eps), reduce_code(reducefn), dh, dw, th, tw,
-        g_volume.data_ptr())
+        "ddrr_siddon_backward_volume", volume.device, *r.vol(volume), *r.rays(), r.ptr(grad_out), B, N,
+        float(voxel_shift), float(eps), reduce_code(reducefn), *hints, g_volume.data_ptr())
     return g_volume
 
 
@@ -782,17 +856,13 @@ def siddon_backward_volume_bricks(volume_shape, source, target, img, grad_out, d
     kernel: every 32^3 brick of the gradient is accumulated in LDS and stored once.
     -> g_volume (Dx,Dy,Dz), fully written"""
     B, N, _ = target.shape
-    H, W = int(det[0]), int(det[1])
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
+    H, W = _grid(det, N, source)
     _require_gpu(target)
-    source, target, grad_out = source.contiguous(), target.contiguous(), grad_out.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _Rays(source, target, img)
     Dx, Dy, Dz = (int(v) for v in volume_shape)
     g_volume = torch.empty(Dx, Dy, Dz, dtype=torch.float32, device=target.device)
-    _launch("ddrr_siddon_backward_volume_bricks", target.device, Dx, Dy, Dz, source.data_ptr(),
-            target.data_ptr(), _ptr(img), grad_out.data_ptr(), B, H, W, float(voxel_shift),
-            float(eps), g_volume.data_ptr(),
+    _launch("ddrr_siddon_backward_volume_bricks", target.device, Dx, Dy, Dz, *r.grid(), r.ptr(grad_out), B, H, W,
+            float(voxel_shift), float(eps), g_volume.data_ptr(),
             launch_workspace((Dx, Dy, Dz), target.device).data_ptr())
     return g_volume
 
@@ -800,20 +870,16 @@ def siddon_backward_volume_bricks(volume_shape, source, target, img, grad_out, d
 def siddon_forward_channels(volume, labels_u8, n_channels, source, target, img, *,
                             voxel_shift=0.5, eps=1e-8, det=None, tile=None):
     """-> (B, C, N)"""
-    B, N = _check_rays(volume, source, target, img)
-    if labels_u8.dtype != torch.uint8 or labels_u8.shape != volume.shape:
-        raise ValueError("labels must be a uint8 tensor of the volume's shape")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    _check_labels(labels_u8, volume)
     out = torch.empty(B, n_channels, N, dtype=torch.float32, device=volume.device)
-    dh, dw, th, tw = _hints(det, tile, N)
+    hints = _hints(det, tile, N)
     if _empty(B, N):
         return out
-    labels_u8, volume = labels_u8.contiguous(), volume.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
     _launch(
-        "ddrr_siddon_forward_channels", volume.device, volume.data_ptr(), labels_u8.data_ptr(),
-        *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,
-        int(n_channels), float(voxel_shift), float(eps), dh, dw, th, tw, out.data_ptr())
+        "ddrr_siddon_forward_channels", volume.device, r.ptr(volume), r.ptr(labels_u8), *volume.shape, *r.rays(),
+        B, N, int(n_channels), float(voxel_shift), float(eps), *hints, out.data_ptr())
     return out
 
 
@@ -890,28 +956,22 @@ def siddon_forward_channels_bricks(volume, labels_u8, n_channels, source, target
     """:func:`siddon_forward_channels` for a detector grid on the volume-stationary brick
     kernel (the label rides in the low byte of the staged voxel word).  ``words``: the volume's
     ready-packed words (:func:`channel_words`) -- staged as they are.  -> (B, C, N)"""
-    B, N = _check_rays(volume, source, target, img)
-    H, W = int(det[0]), int(det[1])
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
-    if labels_u8.dtype != torch.uint8 or labels_u8.shape != volume.shape:
-        raise ValueError("labels must be a uint8 tensor of the volume's shape")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    H, W = _grid(det, N, source)
+    _check_labels(labels_u8, volume)
     out = torch.empty(B, n_channels, N, dtype=torch.float32, device=volume.device)
     if _empty(B, N):
         return out
-    labels_u8, volume = labels_u8.contiguous(), volume.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
     if words is not None:
         if words.shape != volume.shape or words.dtype != torch.float32 or not words.is_contiguous():
             raise ValueError("words: channel_words(volume, labels, n_channels)")
         _launch("ddrr_siddon_forward_channels_bricks_words", volume.device, words.data_ptr(), *volume.shape,
-                source.data_ptr(), target.data_ptr(), _ptr(img), B, H, W, int(n_channels), float(voxel_shift),
-                float(eps), out.data_ptr(), launch_workspace(volume.shape, volume.device).data_ptr())
+                *r.grid(), B, H, W, int(n_channels), float(voxel_shift), float(eps), out.data_ptr(),
+                launch_workspace(volume.shape, volume.device).data_ptr())
         return out
-    _launch("ddrr_siddon_forward_channels_bricks", volume.device, volume.data_ptr(),
-            labels_u8.data_ptr(), *volume.shape, source.data_ptr(), target.data_ptr(), _ptr(img),
-            B, H, W, int(n_channels), float(voxel_shift), float(eps), out.data_ptr(),
+    _launch("ddrr_siddon_forward_channels_bricks", volume.device, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+            *r.grid(), B, H, W, int(n_channels), float(voxel_shift), float(eps), out.data_ptr(),
             launch_workspace(volume.shape, volume.device).data_ptr())
     return out
 
@@ -922,24 +982,18 @@ def siddon_backward_channels_bricks(volume, labels_u8, source, target, img, grad
     volume-stationary bricks: the brick kernel writes the backward record of the volume weighted by
     every voxel's own incoming gradient, ``ddrr_siddon_backward_rays`` turns it into gradients.
     -> (g_source per ray (B,N,3), g_target (B,N,3), g_img (B,N) | None)"""
-    B, N = _check_rays(volume, source, target, img)
-    H, W = int(det[0]), int(det[1])
-    C = grad_out.shape[1]
-    if grad_out.shape != (B, C, N):
-        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    C = _channels(grad_out, B, N)
+    H, W = _grid(det, N, source)
     dev = volume.device
-    aux = torch.empty(record_blocks(B, N), _lib.REC_BLOCK_FLOATS, dtype=torch.float32, device=dev)
+    aux = brick_record_buffer(B, N, dev)
     ones = torch.ones(B, N, dtype=torch.float32, device=dev)
     if not _empty(B, N):
-        labels_u8, volume, grad_out = labels_u8.contiguous(), volume.contiguous(), grad_out.contiguous()
-        source, target = source.contiguous(), target.contiguous()
-        _launch("ddrr_siddon_backward_channels_bricks", dev, volume.data_ptr(), labels_u8.data_ptr(),
-                *volume.shape, source.data_ptr(), target.data_ptr(), grad_out.data_ptr(), B, H, W,
-                int(C), float(voxel_shift), float(eps), aux.data_ptr(),
-                launch_workspace(volume.shape, dev).data_ptr())
-    return siddon_backward_rays(aux, ones, source, target, img, eps=eps, want_img_grad=want_img)
+        _launch("ddrr_siddon_backward_channels_bricks", dev, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+                r.source.data_ptr(), r.target.data_ptr(), r.ptr(grad_out), B, H, W, int(C), float(voxel_shift),
+                float(eps), aux.data_ptr(), launch_workspace(volume.shape, dev).data_ptr())
+    return siddon_backward_rays(aux, ones, r.source, r.target, r.img, eps=eps, want_img_grad=want_img)
 
 
 def siddon_backward_channels_volume_bricks(labels_u8, source, target, img, grad_out, det, *,
@@ -948,22 +1002,14 @@ def siddon_backward_channels_volume_bricks(labels_u8, source, target, img, grad_
     volume-stationary bricks (the LDS brick is the accumulator, the voxel's label rides in the
     word's low byte).  -> g_volume, the label map's shape"""
     B, N, _ = target.shape
-    H, W = int(det[0]), int(det[1])
-    C = grad_out.shape[1]
-    if grad_out.shape != (B, C, N):
-        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
-    if labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3:
-        raise ValueError("labels must be a 3-D uint8 tensor")
+    C = _channels(grad_out, B, N)
+    H, W = _grid(det, N, source)
+    _check_labels(labels_u8)
     _require_gpu(target)
     dev = target.device
-    labels_u8, grad_out = labels_u8.contiguous(), grad_out.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _Rays(source, target, img)
     g_volume = torch.empty(labels_u8.shape, dtype=torch.float32, device=dev)
-    _launch("ddrr_siddon_backward_channels_volume_bricks", dev, labels_u8.data_ptr(),
-            *labels_u8.shape, source.data_ptr(), target.data_ptr(), _ptr(img), grad_out.data_ptr(), B,
+    _launch("ddrr_siddon_backward_channels_volume_bricks", dev, *r.vol(labels_u8), *r.grid(), r.ptr(grad_out), B,
             H, W, int(C), float(voxel_shift), float(eps), g_volume.data_ptr(),
             launch_workspace(labels_u8.shape, dev).data_ptr())
     return g_volume
@@ -979,39 +1025,26 @@ def siddon_backward_midpoint(volume, source, target, img, grad_out, *, voxel_shi
                              want_img=True, want_volume=False):
     """Backward of :func:`siddon_forward` for the midpoint lookups (reduce sum).
     -> (g_source per ray, g_target, g_img, g_volume), None where not asked."""
-    B, N = _check_rays(volume, source, target, img)
-    dev = volume.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume else None
-    if _empty(B, N):
-        return g_source, g_target, g_img, g_volume
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    grad_out = grad_out.contiguous()
-    _launch("ddrr_siddon_backward_midpoint", dev, volume.data_ptr(), *volume.shape,
-            source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), grad_out.data_ptr(),
-            B, N, float(voxel_shift), float(eps), _LOOKUP[lookup], int(bool(align_corners)),
-            _ptr(g_source), _ptr(g_target), _ptr(g_img), _ptr(g_volume))
-    return g_source, g_target, g_img, g_volume
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    g = _grad_buffers(B, N, torch.float32, volume.device, rays=want_rays, img=want_img,
+                      volume_shape=volume.shape if want_volume else None)
+    if not _empty(B, N):
+        _launch("ddrr_siddon_backward_midpoint", volume.device, *r.vol(volume), *r.rays(), r.ptr(grad_out), B, N,
+                float(voxel_shift), float(eps), _LOOKUP[lookup], int(bool(align_corners)), *map(_ptr, g.values()))
+    return tuple(g.values())
 
 
 def siddon_segments(volume, source, target, img, *, voxel_shift=0.5, eps=1e-8):
     """The per-segment terms a callable ``reducefn`` receives (renderers.py:70-71).
     -> (B, M-1, N) with M = Dx+Dy+Dz+3; transpose(1, 2) is the reference's layout."""
-    B, N = _check_rays(volume, source, target, img)
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
     M1 = sum(int(v) for v in volume.shape) + 2
     terms = torch.empty(B, M1, N, dtype=torch.float32, device=volume.device)
-    if _empty(B, N):
-        return terms
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    _launch("ddrr_siddon_segments", volume.device, volume.data_ptr(), *volume.shape,
-            source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,
-            float(voxel_shift), float(eps), terms.data_ptr())
+    if not _empty(B, N):
+        _launch("ddrr_siddon_segments", volume.device, *r.vol(volume), *r.rays(), B, N, float(voxel_shift),
+                float(eps), terms.data_ptr())
     return terms
 
 
@@ -1019,24 +1052,14 @@ def siddon_segments_backward(volume, source, target, img, grad_terms, *, voxel_s
                              want_rays=True, want_img=True, want_volume=False):
     """Backward of :func:`siddon_segments` for grad_terms (B, M-1, N).
     -> (g_source per ray, g_target, g_img, g_volume), None where not asked."""
-    B, N = _check_rays(volume, source, target, img)
-    dev = volume.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume else None
-    if _empty(B, N):
-        return g_source, g_target, g_img, g_volume
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    grad_terms = grad_terms.contiguous()
-    _launch("ddrr_siddon_segments_backward", dev, volume.data_ptr(), *volume.shape,
-            source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-            grad_terms.data_ptr(), B, N, float(voxel_shift), float(eps), _ptr(g_source),
-            _ptr(g_target), _ptr(g_img), _ptr(g_volume))
-    return g_source, g_target, g_img, g_volume
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    g = _grad_buffers(B, N, torch.float32, volume.device, rays=want_rays, img=want_img,
+                      volume_shape=volume.shape if want_volume else None)
+    if not _empty(B, N):
+        _launch("ddrr_siddon_segments_backward", volume.device, *r.vol(volume), *r.rays(), r.ptr(grad_terms), B, N,
+                float(voxel_shift), float(eps), *map(_ptr, g.values()))
+    return tuple(g.values())
 
 
 def siddon_backward_channels(volume, labels_u8, source, target, img, grad_out, *, voxel_shift=0.5,
@@ -1044,29 +1067,18 @@ def siddon_backward_channels(volume, labels_u8, source, target, img, grad_out, *
                              det=None, tile=None):
     """Backward of :func:`siddon_forward_channels` for grad_out (B, C, N).
     -> (g_source per ray (B,N,3), g_target (B,N,3), g_img (B,N), g_volume), None where not asked."""
-    B, N = _check_rays(volume, source, target, img)
-    dev = volume.device
-    C = grad_out.shape[1]
-    if grad_out.shape != (B, C, N):
-        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume else None
-    dh, dw, th, tw = _hints(det, tile, N)
-    if _empty(B, N):
-        return g_source, g_target, g_img, g_volume
-    labels_u8, volume, grad_out = labels_u8.contiguous(), volume.contiguous(), grad_out.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    _launch(
-        "ddrr_siddon_backward_channels", dev, volume.data_ptr(), labels_u8.data_ptr(),
-        *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-        grad_out.data_ptr(), B, N, int(C), float(voxel_shift), float(eps), dh, dw, th, tw,
-        _ptr(g_source), _ptr(g_target), _ptr(g_img), _ptr(g_volume))
-    return g_source, g_target, g_img, g_volume
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    C = _channels(grad_out, B, N)
+    g = _grad_buffers(B, N, torch.float32, volume.device, rays=want_rays, img=want_img,
+                      volume_shape=volume.shape if want_volume else None)
+    hints = _hints(det, tile, N)
+    if not _empty(B, N):
+        _launch(
+            "ddrr_siddon_backward_channels", volume.device, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+            *r.rays(), r.ptr(grad_out), B, N, int(C), float(voxel_shift), float(eps), *hints,
+            *map(_ptr, g.values()))
+    return tuple(g.values())
 
 
 def trilinear_alpha_range(source, target, volume_shape, *, voxel_shift=0.5, eps=1e-8):
@@ -1088,18 +1100,16 @@ def trilinear_forward(volume, source, target, img, alphamin, alphamax, *, n_poin
                       voxel_shift=0.5, eps=1e-8, reducefn="sum", mode="bilinear",
                       align_corners=False, det=None, tile=None):
     """alphamin / alphamax: 0-dim (or 1-element) device tensors.  -> out (B,N)"""
-    B, N = _check_rays(volume, source, target, img)
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
     out = torch.empty(B, N, dtype=torch.float32, device=volume.device)
-    dh, dw, th, tw = _hints(det, tile, N)
+    hints = _hints(det, tile, N)
     if _empty(B, N):
         return out
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
     _launch(
-        "ddrr_trilinear_forward", volume.device, volume.data_ptr(), *volume.shape, source.data_ptr(),
-        source.shape[1], target.data_ptr(), _ptr(img), B, N, float(voxel_shift), float(eps),
+        "ddrr_trilinear_forward", volume.device, *r.vol(volume), *r.rays(), B, N, float(voxel_shift), float(eps),
         int(n_points), alphamin.data_ptr(), alphamax.data_ptr(), int(mode == "nearest"),
-        reduce_code(reducefn), int(bool(align_corners)), dh, dw, th, tw, out.data_ptr())
+        reduce_code(reducefn), int(bool(align_corners)), *hints, out.data_ptr())
     return out
 
 
@@ -1107,21 +1117,17 @@ def trilinear_forward_channels(volume, labels_u8, n_channels, source, target, im
                                alphamax, *, n_points=500, voxel_shift=0.5, eps=1e-8,
                                align_corners=False, det=None, tile=None):
     """Trilinear.forward with a mask (renderers.py:242-252).  -> (B, C, N)"""
-    B, N = _check_rays(volume, source, target, img)
-    if labels_u8.dtype != torch.uint8 or labels_u8.shape != volume.shape:
-        raise ValueError("labels must be a uint8 tensor of the volume's shape")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    _check_labels(labels_u8, volume)
     out = torch.empty(B, n_channels, N, dtype=torch.float32, device=volume.device)
-    dh, dw, th, tw = _hints(det, tile, N)
+    hints = _hints(det, tile, N)
     if _empty(B, N):
         return out
-    labels_u8, volume = labels_u8.contiguous(), volume.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
     _launch(
-        "ddrr_trilinear_forward_channels", volume.device, volume.data_ptr(), labels_u8.data_ptr(),
-        *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,
-        int(n_channels), float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-        alphamax.data_ptr(), int(bool(align_corners)), dh, dw, th, tw, out.data_ptr())
+        "ddrr_trilinear_forward_channels", volume.device, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+        *r.rays(), B, N, int(n_channels), float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
+        alphamax.data_ptr(), int(bool(align_corners)), *hints, out.data_ptr())
     return out
 
 
@@ -1130,28 +1136,18 @@ def trilinear_forward_channels_bricks(volume, labels_u8, n_channels, source, tar
                                       eps=1e-8):
     """The marcher's mask_to_channels for a detector grid on the volume-stationary bricks
     (ddrr_trilinear_forward_channels_bricks; mode "bilinear", align_corners=False).  -> (B, C, N)"""
-    B, N = _check_rays(volume, source, target, img)
-    H, W = int(det[0]), int(det[1])
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
-    if labels_u8.dtype != torch.uint8 or labels_u8.shape != volume.shape:
-        raise ValueError("labels must be a uint8 tensor of the volume's shape")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    H, W = _grid(det, N, source)
+    _check_labels(labels_u8, volume)
     out = torch.empty(B, n_channels, N, dtype=torch.float32, device=volume.device)
     if _empty(B, N):
         return out
-    labels_u8, volume = labels_u8.contiguous(), volume.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
     _launch(
-        "ddrr_trilinear_forward_channels_bricks", volume.device, volume.data_ptr(),
-        labels_u8.data_ptr(), *volume.shape, source.data_ptr(), target.data_ptr(), _ptr(img), B,
-        H, W, int(n_channels), float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-        alphamax.data_ptr(), out.data_ptr(),
-        launch_workspace(volume.shape, volume.device).data_ptr())
+        "ddrr_trilinear_forward_channels_bricks", volume.device, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+        *r.grid(), B, H, W, int(n_channels), float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
+        alphamax.data_ptr(), out.data_ptr(), launch_workspace(volume.shape, volume.device).data_ptr())
     return out
-
-
-TRI_AUX_PLANES = 7  # sum T, sum dT_xyz, sum alpha dT_xyz (include/diffdrr_hip.h)
 
 
 def trilinear_backward_channels_volume_bricks(labels_u8, source, target, img, grad_out, alphamin,
@@ -1161,23 +1157,15 @@ def trilinear_backward_channels_volume_bricks(labels_u8, source, target, img, gr
     owner bricks (LDS accumulator, labels in the words' low byte).  -> g_volume, the label map's
     shape"""
     B, N, _ = target.shape
-    H, W = int(det[0]), int(det[1])
-    C = grad_out.shape[1]
-    if grad_out.shape != (B, C, N):
-        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
-    if labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3:
-        raise ValueError("labels must be a 3-D uint8 tensor")
+    C = _channels(grad_out, B, N)
+    H, W = _grid(det, N, source)
+    _check_labels(labels_u8)
     _require_gpu(target)
     dev = target.device
-    labels_u8, grad_out = labels_u8.contiguous(), grad_out.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _Rays(source, target, img)
     g_volume = torch.empty(labels_u8.shape, dtype=torch.float32, device=dev)
-    _launch("ddrr_trilinear_backward_channels_volume_bricks", dev, labels_u8.data_ptr(),
-            *labels_u8.shape, source.data_ptr(), target.data_ptr(), _ptr(img), grad_out.data_ptr(), B,
-            H, W, int(C), float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
+    _launch("ddrr_trilinear_backward_channels_volume_bricks", dev, *r.vol(labels_u8), *r.grid(), r.ptr(grad_out),
+            B, H, W, int(C), float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
             alphamax.data_ptr(), g_volume.data_ptr(), launch_workspace(labels_u8.shape, dev).data_ptr())
     return g_volume
 
@@ -1190,25 +1178,19 @@ def trilinear_backward_channels_bricks(volume, labels_u8, source, target, img, g
     every sample weighted by the incoming gradient of its channel,
     ``ddrr_trilinear_backward_rays`` turns it into gradients.  Results as
     :func:`trilinear_backward` (without g_volume)."""
-    B, N = _check_rays(volume, source, target, img)
-    H, W = int(det[0]), int(det[1])
-    C = grad_out.shape[1]
-    if grad_out.shape != (B, C, N):
-        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    C = _channels(grad_out, B, N)
+    H, W = _grid(det, N, source)
     dev = volume.device
     aux = torch.empty(TRI_AUX_PLANES, B, N, dtype=torch.float32, device=dev)
     ones = torch.ones(B, N, dtype=torch.float32, device=dev)
     if not _empty(B, N):
-        labels_u8, volume, grad_out = labels_u8.contiguous(), volume.contiguous(), grad_out.contiguous()
-        source, target = source.contiguous(), target.contiguous()
-        _launch("ddrr_trilinear_backward_channels_bricks", dev, volume.data_ptr(),
-                labels_u8.data_ptr(), *volume.shape, source.data_ptr(), target.data_ptr(),
-                grad_out.data_ptr(), B, H, W, int(C), float(voxel_shift), float(eps), int(n_points),
-                alphamin.data_ptr(), alphamax.data_ptr(), aux.data_ptr(),
+        _launch("ddrr_trilinear_backward_channels_bricks", dev, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+                r.source.data_ptr(), r.target.data_ptr(), r.ptr(grad_out), B, H, W, int(C), float(voxel_shift),
+                float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(), aux.data_ptr(),
                 launch_workspace(volume.shape, dev).data_ptr())
-    return trilinear_backward_rays(aux, ones, source, target, img, alphamin, alphamax,
+    return trilinear_backward_rays(aux, ones, r.source, r.target, r.img, alphamin, alphamax,
                                    n_points=n_points, eps=eps, want_rays=want_rays,
                                    want_img=want_img, want_alpha=want_alpha)
 
@@ -1218,21 +1200,16 @@ def trilinear_forward_bricks(volume, source, target, img, alphamin, alphamax, de
     """Detector-grid trilinear march (bilinear, sum, align_corners=False) through the
     volume-stationary brick kernel.  -> out (B,N), or (out, aux (7,B,N)) with ``want_aux``:
     the planar backward record for :func:`trilinear_backward_rays`."""
-    B, N = _check_rays(volume, source, target, img)
-    H, W = int(det[0]), int(det[1])
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    H, W = _grid(det, N, source)
     out = torch.empty(B, N, dtype=torch.float32, device=volume.device)
     aux = torch.empty(TRI_AUX_PLANES, B, N, dtype=torch.float32, device=volume.device) \
         if want_aux else None
     if not _empty(B, N):
-        _launch("ddrr_trilinear_forward_bricks", volume.device, volume.data_ptr(), *volume.shape,
-                source.data_ptr(), target.data_ptr(), _ptr(img), B, H, W, float(voxel_shift),
-                float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(),
-                out.data_ptr(), _ptr(aux),
-                launch_workspace(volume.shape, volume.device).data_ptr())
+        _launch("ddrr_trilinear_forward_bricks", volume.device, *r.vol(volume), *r.grid(), B, H, W,
+                float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(),
+                out.data_ptr(), _ptr(aux), launch_workspace(volume.shape, volume.device).data_ptr())
     return (out, aux) if want_aux else out
 
 
@@ -1242,23 +1219,13 @@ def trilinear_backward_rays(aux, grad_out, source, target, img, alphamin, alpham
     """Ray / range gradients of the march from the record of :func:`trilinear_forward_bricks`;
     results as :func:`trilinear_backward` (without g_volume)."""
     B, N, _ = target.shape
-    dev = target.device
     _require_gpu(target)
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_alpha = new(B, N, 2) if want_alpha else None
-    res = {"g_source": g_source, "g_target": g_target, "g_img": g_img, "g_alpha": g_alpha,
-           "g_volume": None}
-    if _empty(B, N):
-        return res
-    source, target, grad_out = source.contiguous(), target.contiguous(), grad_out.contiguous()
-    img = None if img is None else img.contiguous()
-    _launch("ddrr_trilinear_backward_rays", dev, aux.data_ptr(), grad_out.data_ptr(),
-            source.data_ptr(), target.data_ptr(), _ptr(img), B, N, float(eps), int(n_points),
-            alphamin.data_ptr(), alphamax.data_ptr(), _ptr(g_source), _ptr(g_target), _ptr(g_img),
-            _ptr(g_alpha))
+    res = _grad_buffers(B, N, torch.float32, target.device, rays=want_rays, img=want_img, alpha=want_alpha)
+    if not _empty(B, N):
+        r = _Rays(source, target, img)
+        _launch("ddrr_trilinear_backward_rays", target.device, aux.data_ptr(), r.ptr(grad_out), *r.grid(), B, N,
+                float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(),
+                *(_ptr(res[k]) for k in ("g_source", "g_target", "g_img", "g_alpha")))
     return res
 
 
@@ -1267,17 +1234,13 @@ def trilinear_backward_volume_bricks(volume_shape, source, target, img, grad_out
     """Volume gradient of the detector-grid trilinear march through the brick kernel (LDS
     accumulation).  -> g_volume (Dx,Dy,Dz)"""
     B, N, _ = target.shape
-    H, W = int(det[0]), int(det[1])
-    if H * W != N or source.shape[1] != 1 or min(H, W) < 2:
-        raise ValueError("the brick path needs one source per pose and an H*W >= 2x2 ray grid")
+    H, W = _grid(det, N, source)
     _require_gpu(target)
-    source, target, grad_out = source.contiguous(), target.contiguous(), grad_out.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _Rays(source, target, img)
     Dx, Dy, Dz = (int(v) for v in volume_shape)
     g_volume = torch.empty(Dx, Dy, Dz, dtype=torch.float32, device=target.device)
-    _launch("ddrr_trilinear_backward_volume_bricks", target.device, Dx, Dy, Dz,
-            source.data_ptr(), target.data_ptr(), _ptr(img), grad_out.data_ptr(), B, H, W,
-            float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
+    _launch("ddrr_trilinear_backward_volume_bricks", target.device, Dx, Dy, Dz, *r.grid(), r.ptr(grad_out), B, H,
+            W, float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
             alphamax.data_ptr(), g_volume.data_ptr(),
             launch_workspace((Dx, Dy, Dz), target.device).data_ptr())
     return g_volume
@@ -1287,16 +1250,13 @@ def trilinear_samples(volume, source, target, img, alphamin, alphamax, *, n_poin
                       voxel_shift=0.5, eps=1e-8, mode="bilinear", align_corners=False):
     """The per-sample terms a callable ``reducefn`` of the marcher receives
     (renderers.py:226-238).  -> (B, P, N); transpose(1, 2) is the reference's layout."""
-    B, N = _check_rays(volume, source, target, img)
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
     out = torch.empty(B, int(n_points), N, dtype=torch.float32, device=volume.device)
-    if _empty(B, N):
-        return out
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    _launch("ddrr_trilinear_samples", volume.device, volume.data_ptr(), *volume.shape,
-            source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,
-            float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-            alphamax.data_ptr(), int(mode == "nearest"), int(bool(align_corners)), out.data_ptr())
+    if not _empty(B, N):
+        _launch("ddrr_trilinear_samples", volume.device, *r.vol(volume), *r.rays(), B, N, float(voxel_shift),
+                float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(), int(mode == "nearest"),
+                int(bool(align_corners)), out.data_ptr())
     return out
 
 
@@ -1306,28 +1266,14 @@ def trilinear_samples_backward(volume, source, target, img, grad_samples, alpham
                                want_alpha=True, want_volume=False):
     """Backward of :func:`trilinear_samples` for grad_samples (B, P, N); results as
     :func:`trilinear_backward`."""
-    B, N = _check_rays(volume, source, target, img)
-    dev = volume.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_alpha = new(B, N, 2) if want_alpha else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume else None
-    res = {"g_source": g_source, "g_target": g_target, "g_img": g_img, "g_alpha": g_alpha,
-           "g_volume": g_volume}
-    if _empty(B, N):
-        return res
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    grad_samples = grad_samples.contiguous()
-    _launch("ddrr_trilinear_samples_backward", dev, volume.data_ptr(), *volume.shape,
-            source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-            grad_samples.data_ptr(), B, N, float(voxel_shift), float(eps), int(n_points),
-            alphamin.data_ptr(), alphamax.data_ptr(), int(mode == "nearest"),
-            int(bool(align_corners)), _ptr(g_source), _ptr(g_target), _ptr(g_img), _ptr(g_alpha),
-            _ptr(g_volume))
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    res = _grad_buffers(B, N, torch.float32, volume.device, rays=want_rays, img=want_img, alpha=want_alpha,
+                        volume_shape=volume.shape if want_volume else None)
+    if not _empty(B, N):
+        _launch("ddrr_trilinear_samples_backward", volume.device, *r.vol(volume), *r.rays(), r.ptr(grad_samples),
+                B, N, float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(),
+                int(mode == "nearest"), int(bool(align_corners)), *map(_ptr, res.values()))
     return res
 
 
@@ -1337,32 +1283,17 @@ def trilinear_backward_channels(volume, labels_u8, source, target, img, grad_out
                                 want_alpha=True, want_volume=False, det=None, tile=None):
     """Backward of :func:`trilinear_forward_channels` for grad_out (B, C, N); results as
     :func:`trilinear_backward`."""
-    B, N = _check_rays(volume, source, target, img)
-    dev = volume.device
-    C = grad_out.shape[1]
-    if grad_out.shape != (B, C, N):
-        raise ValueError(f"grad_out must be (B, C, N) = ({B}, C, {N}), got {tuple(grad_out.shape)}")
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_alpha = new(B, N, 2) if want_alpha else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume else None
-    dh, dw, th, tw = _hints(det, tile, N)
-    res = {"g_source": g_source, "g_target": g_target, "g_img": g_img, "g_alpha": g_alpha,
-           "g_volume": g_volume}
-    if _empty(B, N):
-        return res
-    labels_u8, volume, grad_out = labels_u8.contiguous(), volume.contiguous(), grad_out.contiguous()
-    source, target = source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    _launch(
-        "ddrr_trilinear_backward_channels", dev, volume.data_ptr(), labels_u8.data_ptr(),
-        *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-        grad_out.data_ptr(), B, N, int(C), float(voxel_shift), float(eps), int(n_points),
-        alphamin.data_ptr(), alphamax.data_ptr(), int(bool(align_corners)), dh, dw, th, tw,
-        _ptr(g_source), _ptr(g_target), _ptr(g_img), _ptr(g_alpha), _ptr(g_volume))
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    C = _channels(grad_out, B, N)
+    res = _grad_buffers(B, N, torch.float32, volume.device, rays=want_rays, img=want_img, alpha=want_alpha,
+                        volume_shape=volume.shape if want_volume else None)
+    hints = _hints(det, tile, N)
+    if not _empty(B, N):
+        _launch(
+            "ddrr_trilinear_backward_channels", volume.device, r.ptr(volume), r.ptr(labels_u8), *volume.shape,
+            *r.rays(), r.ptr(grad_out), B, N, int(C), float(voxel_shift), float(eps), int(n_points),
+            alphamin.data_ptr(), alphamax.data_ptr(), int(bool(align_corners)), *hints, *map(_ptr, res.values()))
     return res
 
 
@@ -1371,37 +1302,20 @@ def trilinear_backward(volume, source, target, img, grad_out, alphamin, alphamax
                        want_rays=True, want_img=True, want_alpha=True, want_volume=False,
                        det=None, tile=None, reducefn="sum"):
     """-> dict(g_source per ray, g_target, g_img, g_alpha (B,N,2), g_volume)"""
-    B, N = _check_rays(volume, source, target, img)
-    dev = volume.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    g_alpha = new(B, N, 2) if want_alpha else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume else None
-    dh, dw, th, tw = _hints(det, tile, N)
-    res = {"g_source": g_source, "g_target": g_target, "g_img": g_img, "g_alpha": g_alpha,
-           "g_volume": g_volume}
+    r = _rays(volume, source, target, img)
+    B, N = r.B, r.N
+    res = _grad_buffers(B, N, torch.float32, volume.device, rays=want_rays, img=want_img, alpha=want_alpha,
+                        volume_shape=volume.shape if want_volume else None)
+    hints = _hints(det, tile, N)
     if _empty(B, N):
         return res
-    grad_out = grad_out.contiguous()
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    if reduce_code(reducefn) == REDUCE_MAX:
-        _launch(
-            "ddrr_trilinear_backward_max", dev, volume.data_ptr(), *volume.shape,
-            source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), grad_out.data_ptr(),
-            B, N, float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-            alphamax.data_ptr(), int(mode == "nearest"), int(bool(align_corners)),
-            _ptr(g_source), _ptr(g_target), _ptr(g_img), _ptr(g_alpha), _ptr(g_volume))
-        return res
+    # (reduce "max" has no tiled form: no detector hints)
+    maxed = reduce_code(reducefn) == REDUCE_MAX
     _launch(
-        "ddrr_trilinear_backward", dev, volume.data_ptr(), *volume.shape, source.data_ptr(),
-        source.shape[1], target.data_ptr(), _ptr(img), grad_out.data_ptr(), B, N,
-        float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-        alphamax.data_ptr(), int(mode == "nearest"), int(bool(align_corners)), dh, dw, th, tw,
-        _ptr(g_source), _ptr(g_target), _ptr(g_img), _ptr(g_alpha), _ptr(g_volume))
+        "ddrr_trilinear_backward_max" if maxed else "ddrr_trilinear_backward", volume.device, *r.vol(volume),
+        *r.rays(), r.ptr(grad_out), B, N, float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
+        alphamax.data_ptr(), int(mode == "nearest"), int(bool(align_corners)), *(() if maxed else hints),
+        *map(_ptr, res.values()))
     return res
 
 
@@ -1411,16 +1325,14 @@ def trilinear_backward(volume, source, target, img, grad_out, alphamin, alphamax
 def siddon_forward_f64(volume, source, target, img, *, voxel_shift=0.5, eps=1e-8, reducefn="sum",
                        want_aux=False):
     """-> (out (B,N) float64, aux (B,N,8) float64 | None)"""
-    B, N = _check_rays(volume, source, target, img, torch.float64)
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _rays(volume, source, target, img, torch.float64)
+    B, N = r.B, r.N
     out = torch.empty(B, N, dtype=torch.float64, device=volume.device)
     aux = torch.empty(B, N, SIDDON_AUX, dtype=torch.float64, device=volume.device) \
         if want_aux else None
     if not _empty(B, N):
-        _launch("ddrr_siddon_forward_f64", volume.device, volume.data_ptr(), *volume.shape,
-                source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,
-                float(voxel_shift), float(eps), reduce_code(reducefn), out.data_ptr(), _ptr(aux))
+        _launch("ddrr_siddon_forward_f64", volume.device, *r.vol(volume), *r.rays(), B, N, float(voxel_shift),
+                float(eps), reduce_code(reducefn), out.data_ptr(), _ptr(aux))
     return out, aux
 
 
@@ -1428,34 +1340,24 @@ def siddon_backward_f64(volume_shape, source, target, img, grad_out, aux, *, vox
                         eps=1e-8, want_rays=True, want_img=True, want_volume=False):
     """-> (g_source per ray (B,N,3), g_target (B,N,3), g_img (B,N), g_volume), None where not asked"""
     B, N, _ = target.shape
-    dev = target.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img else None
-    Dx, Dy, Dz = (int(v) for v in volume_shape)
-    g_volume = torch.zeros(Dx, Dy, Dz, dtype=torch.float64, device=dev) if want_volume else None
+    dims = tuple(int(v) for v in volume_shape)
+    g = _grad_buffers(B, N, torch.float64, target.device, rays=want_rays, img=want_img,
+                      volume_shape=dims if want_volume else None)
     if not _empty(B, N):
-        source, target, grad_out = source.contiguous(), target.contiguous(), grad_out.contiguous()
-        img = None if img is None else img.contiguous()
-        _launch("ddrr_siddon_backward_f64", dev, Dx, Dy, Dz, source.data_ptr(), source.shape[1],
-                target.data_ptr(), _ptr(img), grad_out.data_ptr(), _ptr(aux), B, N,
-                float(voxel_shift), float(eps), _ptr(g_source), _ptr(g_target), _ptr(g_img),
-                _ptr(g_volume))
-    return g_source, g_target, g_img, g_volume
+        r = _Rays(source, target, img)
+        _launch("ddrr_siddon_backward_f64", target.device, *dims, *r.rays(), r.ptr(grad_out), _ptr(aux), B, N,
+                float(voxel_shift), float(eps), *map(_ptr, g.values()))
+    return tuple(g.values())
 
 
 def trilinear_forward_f64(volume, source, target, img, alphamin, alphamax, *, n_points=500,
                           voxel_shift=0.5, eps=1e-8):
-    B, N = _check_rays(volume, source, target, img, torch.float64)
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
+    r = _rays(volume, source, target, img, torch.float64)
+    B, N = r.B, r.N
     out = torch.empty(B, N, dtype=torch.float64, device=volume.device)
     if not _empty(B, N):
-        _launch("ddrr_trilinear_forward_f64", volume.device, volume.data_ptr(), *volume.shape,
-                source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img), B, N,
-                float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-                alphamax.data_ptr(), out.data_ptr())
+        _launch("ddrr_trilinear_forward_f64", volume.device, *r.vol(volume), *r.rays(), B, N, float(voxel_shift),
+                float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1463,25 +1365,14 @@ def trilinear_backward_f64(volume, source, target, img, grad_out, alphamin, alph
                            n_points=500, voxel_shift=0.5, eps=1e-8, want_rays=True, want_img=True,
                            want_alpha=True, want_volume=False):
     """-> dict(g_source per ray, g_target, g_img, g_alpha (B,N,2), g_volume)"""
-    B, N = _check_rays(volume, source, target, img, torch.float64)
-    dev = volume.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)  # noqa: E731
-    res = {"g_source": new(B, N, 3) if want_rays else None,
-           "g_target": new(B, N, 3) if want_rays else None,
-           "g_img": new(B, N) if want_img else None,
-           "g_alpha": new(B, N, 2) if want_alpha else None,
-           "g_volume": torch.zeros_like(volume, memory_format=torch.contiguous_format)
-           if want_volume else None}
+    r = _rays(volume, source, target, img, torch.float64)
+    B, N = r.B, r.N
+    res = _grad_buffers(B, N, torch.float64, volume.device, rays=want_rays, img=want_img, alpha=want_alpha,
+                        volume_shape=volume.shape if want_volume else None)
     if not _empty(B, N):
-        volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-        img = None if img is None else img.contiguous()
-        grad_out = grad_out.contiguous()
-        _launch("ddrr_trilinear_backward_f64", dev, volume.data_ptr(), *volume.shape,
-                source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-                grad_out.data_ptr(), B, N, float(voxel_shift), float(eps), int(n_points),
-                alphamin.data_ptr(), alphamax.data_ptr(), _ptr(res["g_source"]),
-                _ptr(res["g_target"]), _ptr(res["g_img"]), _ptr(res["g_alpha"]),
-                _ptr(res["g_volume"]))
+        _launch("ddrr_trilinear_backward_f64", volume.device, *r.vol(volume), *r.rays(), r.ptr(grad_out), B, N,
+                float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(), alphamax.data_ptr(),
+                *map(_ptr, res.values()))
     return res
 
 
@@ -1489,27 +1380,25 @@ def trilinear_backward_f64(volume, source, target, img, grad_out, alphamin, alph
 # (csrc/general_rays.hip: the per-segment / per-sample tensors of the reference and their
 # autograd, float32 or float64, for the keyword combinations the fused kernels do not take)
 
-def _general_inputs(volume, source, target, img):
+def _general_rays(volume, source, target, img):
+    """-> (the checked batch, the f64 flag): the general path renders in the volume's dtype."""
     if volume.dtype not in (torch.float32, torch.float64):
         raise TypeError(f"the general path renders float32 or float64, not {volume.dtype}")
-    B, N = _check_rays(volume, source, target, img, volume.dtype)
-    volume, source, target = volume.contiguous(), source.contiguous(), target.contiguous()
-    img = None if img is None else img.contiguous()
-    return B, N, volume, source, target, img, int(volume.dtype == torch.float64)
+    return _rays(volume, source, target, img, volume.dtype), int(volume.dtype == torch.float64)
 
 
 def siddon_segments_general(volume, source, target, img, *, voxel_shift=0.5, eps=1e-8,
                             lookup="step", align_corners=False, raw=False):
     """-> terms (B, M-1, N), M = Dx+Dy+Dz+3: ``img * value * interval`` per segment
     (renderers.py:66-71), or with ``raw`` the looked-up values alone (the label lookup)."""
-    B, N, volume, source, target, img, f64 = _general_inputs(volume, source, target, img)
+    r, f64 = _general_rays(volume, source, target, img)
+    B, N = r.B, r.N
     M1 = sum(volume.shape) + 2
     terms = torch.empty(B, M1, N, dtype=volume.dtype, device=volume.device)
     if not _empty(B, N):
-        _launch("ddrr_siddon_segments_general", volume.device, volume.data_ptr(), f64,
-                *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-                B, N, float(voxel_shift), float(eps), _LOOKUP[lookup], int(bool(align_corners)),
-                int(bool(raw)), terms.data_ptr())
+        _launch("ddrr_siddon_segments_general", volume.device, r.ptr(volume), f64, *volume.shape, *r.rays(), B, N,
+                float(voxel_shift), float(eps), _LOOKUP[lookup], int(bool(align_corners)), int(bool(raw)),
+                terms.data_ptr())
     return terms
 
 
@@ -1518,24 +1407,17 @@ def siddon_segments_general_backward(volume, source, target, img, grad_terms, *,
                                      through_lookup=True, want_rays=True, want_img=True,
                                      want_volume=False):
     """-> (g_source per ray (B,N,3), g_target (B,N,3), g_img (B,N), g_volume), None where not asked"""
-    B, N, volume, source, target, img, f64 = _general_inputs(volume, source, target, img)
-    dev = volume.device
-    new = lambda *s: torch.empty(*s, dtype=volume.dtype, device=dev)  # noqa: E731
-    g_source = new(B, N, 3) if want_rays else None
-    g_target = new(B, N, 3) if want_rays else None
-    g_img = new(B, N) if want_img and through_lookup else None
-    g_volume = torch.zeros_like(volume, memory_format=torch.contiguous_format) \
-        if want_volume and through_lookup else None
+    r, f64 = _general_rays(volume, source, target, img)
+    B, N = r.B, r.N
+    g = _grad_buffers(B, N, volume.dtype, volume.device, rays=want_rays, img=want_img and through_lookup,
+                      volume_shape=volume.shape if want_volume and through_lookup else None)
     if not _empty(B, N):
-        grad_terms = grad_terms.to(volume.dtype).contiguous()
-        _launch("ddrr_siddon_segments_general_backward", dev, volume.data_ptr(), f64,
-                *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-                grad_terms.data_ptr(), B, N, float(voxel_shift), float(eps), _LOOKUP[lookup],
-                int(bool(align_corners)), int(bool(through_lookup)), _ptr(g_source),
-                _ptr(g_target), _ptr(g_img), _ptr(g_volume))
-    elif g_img is not None:
-        g_img.zero_()
-    return g_source, g_target, g_img, g_volume
+        _launch("ddrr_siddon_segments_general_backward", volume.device, r.ptr(volume), f64, *volume.shape,
+                *r.rays(), r.ptr(grad_terms.to(volume.dtype)), B, N, float(voxel_shift), float(eps),
+                _LOOKUP[lookup], int(bool(align_corners)), int(bool(through_lookup)), *map(_ptr, g.values()))
+    elif g["g_img"] is not None:
+        g["g_img"].zero_()
+    return tuple(g.values())
 
 
 def trilinear_samples_general(volume, source, target, img, alphamin, alphamax, *, n_points=500,
@@ -1543,15 +1425,13 @@ def trilinear_samples_general(volume, source, target, img, alphamin, alphamax, *
                               raw=False):
     """-> samples (B, P, N): ``img * step * value`` per sample (renderers.py:224-236), or with
     ``raw`` the looked-up values alone (the label lookup)."""
-    B, N, volume, source, target, img, f64 = _general_inputs(volume, source, target, img)
+    r, f64 = _general_rays(volume, source, target, img)
+    B, N = r.B, r.N
     samples = torch.empty(B, int(n_points), N, dtype=volume.dtype, device=volume.device)
     if not _empty(B, N):
-        alphamin = alphamin.to(volume.dtype).reshape(1).contiguous()
-        alphamax = alphamax.to(volume.dtype).reshape(1).contiguous()
-        _launch("ddrr_trilinear_samples_general", volume.device, volume.data_ptr(), f64,
-                *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-                B, N, float(voxel_shift), float(eps), int(n_points), alphamin.data_ptr(),
-                alphamax.data_ptr(), int(mode == "nearest"), int(bool(align_corners)),
+        _launch("ddrr_trilinear_samples_general", volume.device, r.ptr(volume), f64, *volume.shape, *r.rays(), B,
+                N, float(voxel_shift), float(eps), int(n_points), r.ptr(alphamin.to(volume.dtype).reshape(1)),
+                r.ptr(alphamax.to(volume.dtype).reshape(1)), int(mode == "nearest"), int(bool(align_corners)),
                 int(bool(raw)), samples.data_ptr())
     return samples
 
@@ -1561,40 +1441,20 @@ def trilinear_samples_general_backward(volume, source, target, img, grad_samples
                                        mode="bilinear", align_corners=False, want_rays=True,
                                        want_img=True, want_alpha=True, want_volume=False):
     """-> dict(g_source per ray, g_target, g_img, g_alpha (B,N,2) per ray, g_volume)"""
-    B, N, volume, source, target, img, f64 = _general_inputs(volume, source, target, img)
-    dev = volume.device
-    new = lambda *s: torch.zeros(*s, dtype=volume.dtype, device=dev)  # noqa: E731
-    res = {"g_source": new(B, N, 3) if want_rays else None,
-           "g_target": new(B, N, 3) if want_rays else None,
-           "g_img": new(B, N) if want_img else None,
-           "g_alpha": new(B, N, 2) if want_alpha else None,
-           "g_volume": torch.zeros_like(volume, memory_format=torch.contiguous_format)
-           if want_volume else None}
+    r, f64 = _general_rays(volume, source, target, img)
+    B, N = r.B, r.N
+    res = _grad_buffers(B, N, volume.dtype, volume.device, rays=want_rays, img=want_img, alpha=want_alpha,
+                        volume_shape=volume.shape if want_volume else None, new=torch.zeros)
     if not _empty(B, N):
-        alphamin = alphamin.to(volume.dtype).reshape(1).contiguous()
-        alphamax = alphamax.to(volume.dtype).reshape(1).contiguous()
-        grad_samples = grad_samples.to(volume.dtype).contiguous()
-        _launch("ddrr_trilinear_samples_general_backward", dev, volume.data_ptr(), f64,
-                *volume.shape, source.data_ptr(), source.shape[1], target.data_ptr(), _ptr(img),
-                grad_samples.data_ptr(), B, N, float(voxel_shift), float(eps), int(n_points),
-                alphamin.data_ptr(), alphamax.data_ptr(), int(mode == "nearest"),
-                int(bool(align_corners)), _ptr(res["g_source"]), _ptr(res["g_target"]),
-                _ptr(res["g_img"]), _ptr(res["g_alpha"]), _ptr(res["g_volume"]))
+        _launch("ddrr_trilinear_samples_general_backward", volume.device, r.ptr(volume), f64, *volume.shape,
+                *r.rays(), r.ptr(grad_samples.to(volume.dtype)), B, N, float(voxel_shift), float(eps),
+                int(n_points), r.ptr(alphamin.to(volume.dtype).reshape(1)),
+                r.ptr(alphamax.to(volume.dtype).reshape(1)), int(mode == "nearest"), int(bool(align_corners)),
+                *map(_ptr, res.values()))
     return res
 
 
 # ------------------------------------------------------------------ MutualInformation (libdiffdrr_mi_hip.so)
-def _mi_launch(name, device, *args):
-    """:func:`_launch` through the MutualInformation library (include/diffdrr_mi_hip.h)."""
-    index = device.index
-    current = torch.cuda.current_device()
-    if index is None or index == current:
-        _lib.get_mi_lib().call(name, *args, torch._C._cuda_getCurrentRawStream(current))
-        return
-    with torch.cuda.device(index):
-        _lib.get_mi_lib().call(name, *args, torch._C._cuda_getCurrentRawStream(index))
-
-
 def _mi_image(x, B, N):
     """(B or 1, H, W) -> (tensor, stride in floats): ONE image shared by the batch (an expanded tensor or
     a single image) is read in place with stride 0."""
@@ -1628,9 +1488,9 @@ def mi_forward(x1, x2, bins, sigma, epsilon, normalize, B, want_state=True):
         if n < 0:
             raise ValueError(_lib.get_mi_lib()._last_error().decode(errors="replace"))
         ws = torch.empty((n + 15) // 16, 4, dtype=torch.float32, device=dev)  # (16-byte aligned)
-        _mi_launch("ddrr_mi_forward", dev, a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), K,
-                   sigma.data_ptr(), float(epsilon), int(bool(normalize)), ws.data_ptr(), ws.numel() * 4,
-                   out.data_ptr(), _ptr(state))
+        _launch_on(_lib.get_mi_lib(), "ddrr_mi_forward", dev, (
+            a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), K, sigma.data_ptr(), float(epsilon),
+            int(bool(normalize)), ws.data_ptr(), ws.numel() * 4, out.data_ptr(), _ptr(state)))
     return out, state
 
 
@@ -1640,11 +1500,10 @@ def mi_backward(x1, x2, bins, sigma, state, g_out, which, B):
     H, W = x2.shape[-2:]
     a, s1 = _mi_image(x1, B, H * W)
     b, s2 = _mi_image(x2, B, H * W)
-    g_stride = 0 if (g_out.dim() == 0 or (g_out.dim() == 1 and B > 1 and g_out.stride(0) == 0)) else 1
-    g_out = g_out.contiguous() if g_stride else g_out.reshape(-1)[:1].contiguous()
+    g_out, g_stride = _batch_grad(g_out, B)
     grad = torch.empty(B, H, W, dtype=torch.float32, device=x2.device)
     if B:
-        _mi_launch("ddrr_mi_backward", x2.device, a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(),
-                   bins.numel(), sigma.data_ptr(), state.data_ptr(), int(which), g_out.data_ptr(), g_stride,
-                   grad.data_ptr())
+        _launch_on(_lib.get_mi_lib(), "ddrr_mi_backward", x2.device, (
+            a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), bins.numel(), sigma.data_ptr(),
+            state.data_ptr(), int(which), g_out.data_ptr(), g_stride, grad.data_ptr()))
     return grad

@@ -29,6 +29,61 @@ def test_header_matches_ctypes_signatures():
         assert decls[name] == len(argtypes), name
 
 
+def test_pinned_signatures():
+    """A few entries' complete ctypes types, written out here independently of the header parser of
+    _lib.py: swapping int / long or float / double anywhere in them fails (ctypes would truncate a long
+    above 2^31 or pass a float in the wrong register)."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_void_p
+
+    P, I, F, L, D = c_void_p, c_int, c_float, c_long, c_double
+    pinned = {  # name -> (restype, argtypes)
+        "ddrr_siddon_forward": (I, [P, I, I, I, P, I, P, P, I, I, F, F, I, I, I, I, I, I, I, P, P, P, P]),
+        "ddrr_pose_raygen_forward": (I, [P, P, I, I, I, P, P, P, I, I, P, P, P, P, P, L, P, P]),
+        "ddrr_siddon_forward_f64": (I, [P, I, I, I, P, I, P, P, I, I, D, D, I, P, P, P]),
+        "ddrr_brick_workspace_bytes": (L, [I, I, I, I]),
+        "ddrr_siddon_ncc_workspace_bytes": (L, [I]),
+        "ddrr_channel_words_state_bytes": (L, []),
+        "ddrr_last_error": (c_char_p, []),
+        "ddrr_abi_version": (I, []),
+    }
+    assert len(pinned["ddrr_siddon_forward"][1]) == 23
+    for name, (restype, argtypes) in pinned.items():
+        assert _lib.HEADER.restypes[name] is restype, name
+        assert _lib.HEADER.argtypes[name] == argtypes, name
+        if name in _lib._SIGNATURES:
+            assert _lib._SIGNATURES[name] == argtypes, name
+            assert _lib._RESTYPES.get(name, c_int) is restype, name
+    mi = {"ddrr_mi_forward": (I, [P, L, P, L, I, I, I, P, I, P, F, I, P, L, P, P, P]),
+          "ddrr_mi_workspace_bytes": (L, [I, I, I, I]),
+          "ddrr_mi_last_error": (c_char_p, [])}
+    for name, (restype, argtypes) in mi.items():
+        assert _lib.MI_HEADER.restypes[name] is restype, name
+        assert _lib.MI_HEADER.argtypes[name] == argtypes, name
+    assert _lib._MI_SIGNATURES["ddrr_mi_forward"] == mi["ddrr_mi_forward"][1]
+    assert _lib._MI_RESTYPES["ddrr_mi_workspace_bytes"] is L
+
+
+@pytest.mark.parametrize("decl", [
+    "int ddrr_bad(const float *x, size_t n, void *stream);",
+    "int ddrr_bad(const float *x, unsigned n, void *stream);",
+    "int ddrr_bad(const float *x, void (*done)(void *), void *stream);",
+    "unsigned ddrr_bad(int n);",
+])
+def test_header_parser_refuses_what_it_cannot_map(decl):
+    """The binding never guesses a type: a parameter or result it has no exact ctypes mapping for is an
+    error that names the entry."""
+    text = f"/* a header */\n#define DDRR_X 1\nint ddrr_good(int a, long b, void *stream);\n{decl}\n"
+    with pytest.raises(ValueError, match="ddrr_bad"):
+        _lib.parse_header(text)
+    good = _lib.parse_header(text.replace(decl, ""))
+    assert good[0] == {"ddrr_good": [_lib._I, _lib._L, _lib._P]} and good[2] == {"DDRR_X": 1}
+
+
+def test_header_version_must_be_the_bindings():
+    with pytest.raises(RuntimeError, match="DDRR_ABI_VERSION"):
+        _lib.Header.read("diffdrr_hip.h", "ddrr", _lib.ABI_VERSION - 1)
+
+
 def test_header_constants_match():
     text = open(HEADER).read()
     const = dict(re.findall(r"#define (DDRR_\w+) (\d+)", text))
