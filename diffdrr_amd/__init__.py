@@ -16,5 +16,11 @@ from .metrics import (  # noqa: F401
     NormalizedCrossCorrelation2d,
 )
 from .pose import RigidTransform, convert  # noqa: F401
+from .reconstruction import (  # noqa: F401
+    Reconstruction,
+    TotalVariation3d,
+    VolumeAdam,
+    total_variation_3d,
+)
 from .registration import GraphedIteration, PoseAdam, Registration  # noqa: F401
 from .renderers import Siddon, Trilinear  # noqa: F401

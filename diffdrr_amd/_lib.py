@@ -27,6 +27,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_hip.so")
 # own must both be these (checked on import and on load).
 ABI_VERSION = 33
 MI_ABI_VERSION = 1
+RECON_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -200,3 +201,34 @@ def get_mi_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _mi_lib = mi_library(MI_LIB_PATH)
     return _mi_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_recon_hip.so
+# Reconstruction: total variation and the volume's Adam step (C ABI: include/diffdrr_recon_hip.h)
+RECON_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_recon_hip.so")
+RECON_HEADER = Header.read("diffdrr_recon_hip.h", "ddrr_recon", RECON_ABI_VERSION)
+_RECON_SIGNATURES, _RECON_RESTYPES, RECON_EXPORTS = RECON_HEADER.tables()
+RECON_TV_ISOTROPIC, RECON_TV_ANISOTROPIC, RECON_MAX_DIM = RECON_HEADER.constants(
+    "TV_ISOTROPIC", "TV_ANISOTROPIC", "MAX_DIM")
+
+
+def recon_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_recon_hip.h."""
+    return DdrrLibrary(path, RECON_HEADER)
+
+
+_recon_lib: DdrrLibrary | None = None
+
+
+def get_recon_lib() -> DdrrLibrary:
+    """The reconstruction library, loaded on first use.  Raises if it has not been built."""
+    global _recon_lib
+    if _recon_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(RECON_LIB_PATH):
+            raise RuntimeError(
+                f"{RECON_LIB_PATH} is missing: the reconstruction kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _recon_lib = recon_library(RECON_LIB_PATH)
+    return _recon_lib

@@ -1507,3 +1507,81 @@ def mi_backward(x1, x2, bins, sigma, state, g_out, which, B):
             a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), bins.numel(), sigma.data_ptr(),
             state.data_ptr(), int(which), g_out.data_ptr(), g_stride, grad.data_ptr()))
     return grad
+
+
+# ------------------------------------------------------------------ reconstruction (libdiffdrr_recon_hip.so)
+_TV_MODES = {"isotropic": _lib.RECON_TV_ISOTROPIC, "anisotropic": _lib.RECON_TV_ANISOTROPIC}
+
+
+def _check_volume_like(name, t, like=None):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous float32 tensor expected")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{name}: shape {tuple(t.shape)} on {t.device}, expected {tuple(like.shape)} on {like.device}")
+
+
+def tv3d(volume, spacing=(1.0, 1.0, 1.0), mode="isotropic", eps=1e-3, grad=None, accumulate=False, weight=1.0,
+         scale=None):
+    """3-D total variation of `volume` (Dx, Dy, Dz) fp32 on the device, and its gradient in the same pass
+    (include/diffdrr_recon_hip.h ddrr_recon_tv3d): `grad` None -> the value only; else `grad` (same shape)
+    = w dTV/dV, or += w dTV/dV with `accumulate`, where w = weight * scale (`scale`: a 1-element device
+    tensor or None, read on the device).  -> the unweighted value, a 0-dim device tensor."""
+    if not torch.is_tensor(volume) or volume.dim() != 3:
+        raise ValueError("tv3d: a (Dx, Dy, Dz) volume expected")
+    _check_volume_like("tv3d: volume", volume)
+    _require_gpu(volume)
+    if mode not in _TV_MODES:
+        raise ValueError(f"tv3d: mode must be 'isotropic' or 'anisotropic', not {mode!r}")
+    spacing = tuple(float(s) for s in spacing)
+    if len(spacing) != 3 or not all(0.0 < s < float("inf") for s in spacing):
+        raise ValueError(f"tv3d: spacing must be three positive numbers, not {spacing}")
+    if not 0.0 <= float(eps) < float("inf"):
+        raise ValueError(f"tv3d: eps must be >= 0, not {eps}")
+    if max(volume.shape) > _lib.RECON_MAX_DIM or volume.numel() > 2**34:
+        raise ValueError(f"tv3d: at most {_lib.RECON_MAX_DIM} voxels per axis and 2^34 in all, got {tuple(volume.shape)}")
+    if grad is not None:
+        _check_volume_like("tv3d: grad", grad, volume)
+    elif accumulate:
+        raise ValueError("tv3d: accumulate needs a grad tensor")
+    if scale is not None:
+        if (not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1
+                or scale.device != volume.device):
+            raise ValueError("tv3d: scale must be a 1-element float32 tensor on the volume's device")
+    dev = volume.device
+    if volume.numel() == 0:
+        return torch.zeros((), dtype=torch.float32, device=dev)
+    lib = _lib.get_recon_lib()
+    dims = tuple(int(d) for d in volume.shape)
+    n = int(lib.query("ddrr_recon_tv_workspace_bytes", *dims))
+    if n < 0:
+        raise ValueError(lib._last_error().decode(errors="replace"))
+    ws = torch.empty((n + 15) // 16, 2, dtype=torch.float64, device=dev)  # (16-byte aligned)
+    value = torch.empty((), dtype=torch.float32, device=dev)
+    _launch_on(lib, "ddrr_recon_tv3d", dev, (
+        volume.data_ptr(), *dims, *spacing, _TV_MODES[mode], float(eps), _ptr(grad), int(bool(accumulate)),
+        float(weight), _ptr(scale), ws.data_ptr(), ws.numel() * 8, value.data_ptr()))
+    return value
+
+
+def volume_adam_step(param, grad, exp_avg, exp_avg_sq, step, *, lr, betas=(0.9, 0.999), eps=1e-8, lower=None,
+                     upper=None, maximize=False):
+    """One Adam step of `param` (any shape, fp32, contiguous, on the device) in place, then its projection
+    onto [lower, upper] (None = no bound), in one pass (include/diffdrr_recon_hip.h ddrr_recon_adam_step:
+    torch.optim.Adam's update; `step` is a 1-element float tensor on the device, incremented there)."""
+    _check_volume_like("volume_adam_step: param", param)
+    _require_gpu(param)
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _check_volume_like(f"volume_adam_step: {name}", t, param)
+    if (not torch.is_tensor(step) or step.dtype != torch.float32 or step.numel() != 1
+            or step.device != param.device):
+        raise ValueError("volume_adam_step: a 1-element float32 step counter on the parameter's device")
+    lo = float("-inf") if lower is None else float(lower)
+    hi = float("inf") if upper is None else float(upper)
+    if not lo <= hi:
+        raise ValueError(f"volume_adam_step: lower {lower} must be <= upper {upper}")
+    if not (float(lr) >= 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and float(eps) >= 0.0):
+        raise ValueError("volume_adam_step: invalid lr / betas / eps")
+    if param.numel():
+        _launch_on(_lib.get_recon_lib(), "ddrr_recon_adam_step", param.device, (
+            param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step.data_ptr(),
+            param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), lo, hi, int(bool(maximize))))
