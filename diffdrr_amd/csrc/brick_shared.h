@@ -4,6 +4,8 @@
 // helpers, and the delivery of the float backward record.
 #pragma once
 
+#include <mutex>
+
 #include "runtime.h"
 #include "brick_core.h"
 #include "brick_walk.h"
@@ -208,26 +210,28 @@ __device__ __forceinline__ void wave_fence() {
 
 #endif  // __HIPCC__
 
-// This launch's device-side state, carved out of the caller's launch workspace (bricks.hip): the
-// CU count and the brick counter {brick id, wmax bits, n_sum, -}, zeroed on `st`;
-// order_ws / order_cap: the room for the hand-out order of the bricks (bricks_fwd.hip).
-long brick_launch_workspace_bytes(int dx, int dy, int dz);
-int brick_launch_resources(hipStream_t st, void *launch_ws, int dx, int dy, int dz, int &n_cu,
-                           int *&work, int **order_ws = nullptr, int *order_cap = nullptr,
-                           bool zero_work = true);
+// One brick launch as its entry point describes it: the members every launch has first (an entry
+// brace-initialises those, in this order), then what only some modes take, each set by name.
+struct BrickLaunch {
+    const float *volume;
+    int dx, dy, dz;
+    const float *source, *target, *img;
+    int B, det_h, det_w;
+    float shift, eps;
+    hipStream_t st;
+    void *launch_ws;  // ddrr_brick_launch_workspace_bytes
+    const char *who;  // the entry's name, for its error messages
+    const float *grad_out = nullptr;
+    float *out = nullptr, *aux = nullptr, *g_volume = nullptr;
+    int n_points = 0;
+    const float *amin = nullptr, *amax = nullptr;
+    float rec_q = 0.f;
+    const unsigned char *labels = nullptr;
+    int n_channels = 0;
+    const unsigned *pix_mask = nullptr;
+};
 
-// The 32^3 fp32 launch path of bricks.hip (every mode); bricks_fwd.hip falls back to it.
-bool order_bricks(BrickArgs &q, int BX, int BY, int BZ, int nby, int nbz, int n_bricks, int slots,
-                  hipStream_t st, bool zero_counter = false, int min_poses = 8);
-int launch_bricks(int mode, const float *volume, int dx, int dy, int dz, const float *source,
-                  const float *target, const float *img, const float *grad_out, int B, int det_h,
-                  int det_w, float voxel_shift, float eps, float *out, float *aux,
-                  float *g_volume, hipStream_t st, void *launch_ws, const char *who, int n_points = 0,
-                  const float *amin = nullptr, const float *amax = nullptr, float rec_q = 0.f,
-                  const unsigned char *labels = nullptr, int n_channels = 0,
-                  const unsigned *pix_mask = nullptr);
-
-// The configurable Siddon forward / forward + record kernel (bricks_fwd.hip).  variant:
+// What only the storage of the configurable forward kernel has (bricks_fwd.hip).  variant:
 // DDRR_BRICKS_F32 / DDRR_BRICKS_Q16 (fp32 bricks at fewer than 8 poses, and volumes of fewer than four
 // voxels, take launch_bricks).
 // brick_ranges: the DDRR_BRICKS_Q16 workspace (header, (min, max) and fallback flag per brick),
@@ -236,20 +240,63 @@ int launch_bricks(int mode, const float *volume, int dx, int dy, int dz, const f
 // clear, clear_n: floats the launch has to find zeroed (the image or the record its atomics add to):
 // cleared by the launch that clears the brick counter -- one launch instead of two memsets, each
 // of which is a launch of its own (5 us apiece in front of a 140 us one-pose render).
+struct FwdStorage {
+    int variant, packed;
+    float *brick_ranges;
+    int ranges_valid;
+    float *clear;
+    long clear_n;
+};
+
+// The kernel argument of a launch: everything zero but the launch's own description, the record's
+// plane size, the queue entry's split and the experiment switches; refuses a pose batch whose ray
+// indices do not fit the queue entries.  The launchers add what is theirs.
+int brick_args(const BrickLaunch &l, BrickArgs &p);
+
+// This launch's device-side state, carved out of the caller's launch workspace (bricks.hip): the
+// brick counter {brick id, wmax bits, n_sum, -}, zeroed on the launch's stream, and the room for
+// the hand-out order of the bricks (bricks_fwd.hip); dev, n_cu: the current device and its CU count.
+long brick_launch_workspace_bytes(int dx, int dy, int dz);
+int brick_launch_resources(const BrickLaunch &l, BrickArgs &p, int &dev, int &n_cu, bool zero_work = true);
+
+// "Once per device": the state of one thing that is done at a device's first launch -- a
+// function-local static of the launcher, so one per instantiation of a launcher template, i.e. per
+// kernel -- and the one thing the brick launchers do that way, the raised dynamic-LDS limit.
+constexpr int kMaxDev = 64;
+int current_device(int &dev);  // range-checked against kMaxDev
+struct OncePerDevice {
+    std::mutex mu;
+    bool done[kMaxDev] = {false};
+};
+template <class F>  // int f(): 0 or an error code (then it is tried again at the next launch)
+int once_per_device(OncePerDevice &once, int dev, F f) {
+    std::lock_guard<std::mutex> lock(once.mu);
+    if (once.done[dev]) return 0;
+    if (int rc = f()) return rc;
+    once.done[dev] = true;
+    return 0;
+}
+template <class K>
+int raise_lds_limit(K *kernel, int bytes) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e == hipSuccess ? 0 : ddrr_rt::fail_hip(e, "hipFuncSetAttribute");
+}
+
+// The 32^3 fp32 launch path of bricks.hip (every mode); bricks_fwd.hip falls back to it.
+bool order_bricks(BrickArgs &q, int BX, int BY, int BZ, int nby, int nbz, int n_bricks, int slots,
+                  hipStream_t st, bool zero_counter = false, int min_poses = 8);
+int launch_bricks(int mode, const BrickLaunch &l);
+
+// The configurable Siddon forward / forward + record kernel (bricks_fwd.hip).
 long brick_workspace_bytes(int dx, int dy, int dz, int brick_storage);
-int launch_fwd_bricks(int variant, int packed, float *brick_ranges, int ranges_valid, const float *volume,
-                      int dx, int dy, int dz, const float *source, const float *target,
-                      const float *img, int B, int det_h, int det_w, float voxel_shift, float eps,
-                      float *out, float *aux, float rec_q, hipStream_t st, void *launch_ws,
-                      const char *who, float *clear = nullptr, long clear_n = 0,
-                      const unsigned *pix_mask = nullptr);
+int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s);
 
 // experiment switches (tools builds: mutable; product: constants)
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
 extern float g_brick_t1, g_brick_t2;
 extern int g_brick_dbg;
 extern int g_brick_variant;
-extern float g_brick_sq_width;
 extern const int *g_brick_order;
 extern unsigned *g_brick_times;  // profiling builds: per-brick duration, 10 ns ticks
 extern int g_brick_split_t, g_brick_split_s;

@@ -4,7 +4,6 @@
 // gradients, trilinear forward (+ record); and the elementwise kernels that consume the records.
 #include "runtime.h"
 
-#include <mutex>
 #include "siddon_core.h"
 #include "brick_core.h"
 #include "brick_walk.h"
@@ -1065,7 +1064,6 @@ namespace ddrr_brick {
 float g_brick_t1 = 18.f, g_brick_t2 = 40.f;
 int g_brick_dbg = 0;
 int g_brick_variant = -2;
-float g_brick_sq_width = 8.f;
 const int *g_brick_order = nullptr;
 unsigned *g_brick_times = nullptr;
 int g_brick_split_t = 0, g_brick_split_s = 1;
@@ -1085,17 +1083,20 @@ long brick_launch_workspace_bytes(int dx, int dy, int dz) {
     return 256 + (n32 * 2 * (long)sizeof(int) + 255) / 256 * 256;
 }
 
-int brick_launch_resources(hipStream_t st, void *launch_ws, int dx, int dy, int dz, int &n_cu_out,
-                           int *&work, int **order_ws, int *order_cap, bool zero_work) {
-    constexpr int kMaxDev = 64;
+int current_device(int &dev) {
+    const hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+    if (dev < 0 || dev >= kMaxDev) return fail(-1, "device index out of range");
+    return 0;
+}
+
+int brick_launch_resources(const BrickLaunch &l, BrickArgs &p, int &dev, int &n_cu_out, bool zero_work) {
     static std::mutex mu;
     static int n_cu[kMaxDev] = {0};
     hipError_t e;
-    int dev = 0;
-    if (!launch_ws) return fail(-1, "null launch workspace (ddrr_brick_launch_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(launch_ws) & 15) return fail(-1, "launch workspace not 16-byte aligned");
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return fail_hip(e, "hipGetDevice");
-    if (dev < 0 || dev >= kMaxDev) return fail(-1, "device index out of range");
+    if (!l.launch_ws) return fail(-1, "null launch workspace (ddrr_brick_launch_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(l.launch_ws) & 15) return fail(-1, "launch workspace not 16-byte aligned");
+    if (int rc = current_device(dev)) return rc;
     {
         std::lock_guard<std::mutex> lock(mu);
         if (!n_cu[dev] &&
@@ -1104,172 +1105,135 @@ int brick_launch_resources(hipStream_t st, void *launch_ws, int dx, int dy, int 
             return fail_hip(e, "hipDeviceGetAttribute");
         n_cu_out = n_cu[dev];
     }
-    work = reinterpret_cast<int *>(launch_ws);
-    if (order_ws) {
-        *order_ws = work + 64;
-        *order_cap = (int)(((long)((dx + 31) / 32) * ((dy + 31) / 32)) * ((dz + 31) / 32));
-    }
+    p.work = reinterpret_cast<int *>(l.launch_ws);
+    p.order_ws = p.work + 64;
+    p.order_cap = (int)(((long)((l.dx + 31) / 32) * ((l.dy + 31) / 32)) * ((l.dz + 31) / 32));
+    if (g_brick_dbg & 512) p.order_ws = nullptr;  // (bricks in id order)
     // (zero_work = false: the caller clears the counter itself, bricks_fwd.hip launch_cfg)
-    if (zero_work && (e = hipMemsetAsync(work, 0, 4 * sizeof(int), st)) != hipSuccess)
+    if (zero_work && (e = hipMemsetAsync(p.work, 0, 4 * sizeof(int), l.st)) != hipSuccess)
         return fail_hip(e, "hipMemsetAsync");
     return 0;
 }
 
-int launch_bricks(int mode, const float *volume, int dx, int dy, int dz, const float *source,
-                  const float *target, const float *img, const float *grad_out, int B, int det_h,
-                  int det_w, float voxel_shift, float eps, float *out, float *aux,
-                  float *g_volume, hipStream_t st, void *launch_ws, const char *who, int n_points,
-                  const float *amin, const float *amax, float rec_q,
-                  const unsigned char *labels, int n_channels, const unsigned *pix_mask) {
-    const int N = det_h * det_w;
-    BrickArgs p;
-    p.pix_mask = pix_mask;
-    p.fingerprint = nullptr;
-    p.vol = volume;
-    p.D = Dims{dx, dy, dz};
-    p.source = source;
-    p.target = target;
-    p.img = img;
-    p.B = B;
-    p.det_h = det_h;
-    p.det_w = det_w;
-    p.shift = voxel_shift;
-    p.eps = eps;
-    p.lay = g_brick_layout;
-    if ((long)B * N * 12 >= (1L << 32))
+int brick_args(const BrickLaunch &l, BrickArgs &p) {
+    const long N = (long)l.det_h * l.det_w;
+    p = BrickArgs{};
+    p.vol = l.volume;
+    p.D = Dims{l.dx, l.dy, l.dz};
+    p.source = l.source;
+    p.target = l.target;
+    p.img = l.img;
+    p.B = l.B;
+    p.det_h = l.det_h;
+    p.det_w = l.det_w;
+    p.shift = l.shift;
+    p.eps = l.eps;
+    p.grad_out = l.grad_out;
+    p.g_volume = l.g_volume;
+    p.n_points = l.n_points;
+    p.amin = l.amin;
+    p.amax = l.amax;
+    p.rec_q = l.rec_q;
+    p.labels = l.labels;
+    p.n_channels = l.n_channels;
+    p.pix_mask = l.pix_mask;
+    if (l.B * N * 12 >= (1L << 32))
         return fail(-1, "B * N too large for one brick launch (12 B N must stay below 2^32): "
                         "split the pose batch");
-    p.aux_plane = (unsigned)((long)B * N);
-    p.rec_q = rec_q;
+    p.aux_plane = (unsigned)(l.B * N);
     p.pix_bits = 1;
     while ((1L << p.pix_bits) < N) ++p.pix_bits;
-    if (((long)B << p.pix_bits) > (1L << 32))
+    if (((long)l.B << p.pix_bits) > (1L << 32))
         return fail(-1, "B * 2^ceil(log2 N) exceeds 2^32: split the pose batch");
     p.t1 = g_brick_t1;
     p.t2 = g_brick_t2;
     p.dbg = g_brick_dbg;
-    p.grad_out = grad_out;
-    p.g_volume = g_volume;
-    p.n_points = n_points;
-    p.amin = amin;
-    p.amax = amax;
-    p.prof = nullptr;
-    p.labels = labels;
-    p.n_channels = n_channels;
-    p.ranges = nullptr;
-    p.fallback = nullptr;
-    p.ws_header = nullptr;
-    p.ranges_valid = 0;
-    p.brick_times = nullptr;
-#if defined(DDRR_BRICK_PROFILE)
+    p.split_s = 1;
+#if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
     p.brick_times = g_brick_times;
 #endif
-    p.order = nullptr;
-    p.order_ws = nullptr;
-    p.order_cap = 0;
-    p.split_t = 0;
-    p.split_s = 1;
 #if defined(DDRR_BRICK_PROFILE)
     p.prof = g_brick_prof;
 #endif
-    if (mode == BRICK_TRI_FWD || mode == BRICK_TRI_VOLGRAD || mode == BRICK_TRI_FWD_AUX ||
-        mode == BRICK_TRI_CHANNELS || mode == BRICK_TRI_CHANNELS_AUX || mode == BRICK_TRI_CHANNELS_VOLGRAD) {
+    return 0;
+}
+
+namespace {
+
+// The modes of siddon_brick_kernel and what the launcher has to know about each.
+struct BrickMode {
+    int mode;
+    void (*kernel)(BrickArgs, float *, float *);
+    bool marcher;   // the trilinear marcher (its length classes count samples, not crossings)
+    bool tri_grid;  // bricks of cells + halo (tri_brick.h tri_brick_grid) instead of the plain grid
+    int prepare;    // volgrad_prepare_kernel in front: 0 no, 1 yes, 2 with the channels of grad_out
+    int order_min_poses;  // bricks handed out heaviest first from so many poses on (0: in id order)
+};
+template <int MODE>
+constexpr BrickMode brick_mode(bool marcher, bool tri_grid, int prepare, int order_min_poses) {
+    return {MODE, &siddon_brick_kernel<MODE>, marcher, tri_grid, prepare, order_min_poses};
+}
+// The Siddon modes hand their bricks out heaviest first like the forward kernels.  The marcher's
+// forward bricks are cells + halo with their own boxes: id order; its volume gradient works on
+// owner bricks = the plain grid, and a brick's walks are long whatever the pose count.
+// (Newest mode first: the order in which the kernels have always been laid out in the code object.)
+constexpr BrickMode kBrickModes[] = {
+    brick_mode<BRICK_CHANNELS_WORDS>(false, false, 0, 8),
+    brick_mode<BRICK_TRI_CHANNELS_VOLGRAD>(true, false, 2, 0),
+    brick_mode<BRICK_CHANNELS_VOLGRAD>(false, false, 2, 8),
+    brick_mode<BRICK_TRI_CHANNELS_AUX>(true, true, 0, 0),
+    brick_mode<BRICK_CHANNELS_AUX>(false, false, 0, 8),
+    brick_mode<BRICK_TRI_CHANNELS>(true, true, 0, 0),
+    brick_mode<BRICK_CHANNELS>(false, false, 0, 8),
+    brick_mode<BRICK_TRI_FWD_AUX>(true, true, 0, 0),
+    brick_mode<BRICK_FWD>(false, false, 0, 8),
+    brick_mode<BRICK_FWD_AUX>(false, false, 0, 8),
+    brick_mode<BRICK_VOLGRAD>(false, false, 1, 8),
+    brick_mode<BRICK_TRI_FWD>(true, true, 0, 0),
+    brick_mode<BRICK_TRI_VOLGRAD>(true, false, 1, 1),
+};
+
+}  // namespace
+
+int launch_bricks(int mode, const BrickLaunch &l) {
+    const BrickMode *m = nullptr;
+    for (const BrickMode &row : kBrickModes)
+        if (row.mode == mode) m = &row;
+    if (!m) return fail(-1, "unknown brick mode");
+    BrickArgs p;
+    if (int rc = brick_args(l, p)) return rc;
+    p.lay = g_brick_layout;
+    if (m->marcher) {
         p.t1 = g_tri_t1;
         p.t2 = g_tri_t2;
     }
     const size_t lds = brick_lds_bytes(p.lay);
-    hipError_t e;
-    // the raised dynamic-LDS limit of the brick kernels, once per device
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_set[kMaxDev] = {false};
-    int dev = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return fail_hip(e, "hipGetDevice");
-    if (dev < 0 || dev >= kMaxDev) return fail(-1, "device index out of range");
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            const void *fns[13] = {
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_CHANNELS_WORDS>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_TRI_CHANNELS_VOLGRAD>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_CHANNELS_VOLGRAD>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_TRI_CHANNELS_AUX>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_CHANNELS_AUX>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_TRI_CHANNELS>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_CHANNELS>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_TRI_FWD_AUX>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_FWD>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_FWD_AUX>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_VOLGRAD>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_TRI_FWD>),
-                reinterpret_cast<const void *>(&siddon_brick_kernel<BRICK_TRI_VOLGRAD>)};
-            for (const void *fn : fns)
-                if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024)) != hipSuccess)
-                    return fail_hip(e, "hipFuncSetAttribute");
-            attr_set[dev] = true;
-        }
-    }
-    int n_cu_dev = 0;
-    if (int rc = brick_launch_resources(st, launch_ws, dx, dy, dz, n_cu_dev, p.work, &p.order_ws, &p.order_cap))
+    int dev = 0, n_cu = 0;
+    if (int rc = brick_launch_resources(l, p, dev, n_cu)) return rc;
+    // every mode's limit at the first launch of any: a warm-up in one mode also prepares a mode
+    // whose first launch may fall inside a stream capture
+    static OncePerDevice lds_limit;
+    if (int rc = once_per_device(lds_limit, dev, [] {
+            for (const BrickMode &row : kBrickModes)
+                if (int r = raise_lds_limit(row.kernel, 160 * 1024)) return r;
+            return 0;
+        }))
         return rc;
-    if (g_brick_dbg & 512) p.order_ws = nullptr;  // (bricks in id order)
-    if (mode == BRICK_VOLGRAD || mode == BRICK_TRI_VOLGRAD || mode == BRICK_CHANNELS_VOLGRAD ||
-        mode == BRICK_TRI_CHANNELS_VOLGRAD) {
-        const int tri = mode == BRICK_TRI_VOLGRAD || mode == BRICK_TRI_CHANNELS_VOLGRAD;
+    if (m->prepare) {
+        const int N = l.det_h * l.det_w;
         int bx = (N + kBlock - 1) / kBlock;
         bx = bx > 64 ? 64 : bx;
-        hipLaunchKernelGGL(volgrad_prepare_kernel, dim3(bx, B), dim3(kBlock), 0, st, tri, source,
-                           target, img, grad_out, N, det_w, p.D, voxel_shift, eps, n_points, amin,
-                           amax, p.work,
-                           mode == BRICK_CHANNELS_VOLGRAD || mode == BRICK_TRI_CHANNELS_VOLGRAD ? n_channels : 0);
+        hipLaunchKernelGGL(volgrad_prepare_kernel, dim3(bx, l.B), dim3(kBlock), 0, l.st, (int)m->marcher,
+                           l.source, l.target, l.img, l.grad_out, N, l.det_w, p.D, l.shift, l.eps,
+                           l.n_points, l.amin, l.amax, p.work, m->prepare == 2 ? l.n_channels : 0);
     }
-    const BrickGrid bg = (mode == BRICK_TRI_FWD || mode == BRICK_TRI_FWD_AUX ||
-                          mode == BRICK_TRI_CHANNELS || mode == BRICK_TRI_CHANNELS_AUX)
-                             ? tri_brick_grid(p.D)
-                                                                              : brick_grid(p.D);
+    const BrickGrid bg = m->tri_grid ? tri_brick_grid(p.D) : brick_grid(p.D);
     const int n_bricks = bg.nx * bg.ny * bg.nz;
-    // the Siddon modes hand their bricks out heaviest first like the forward kernels (the marcher's
-    // bricks are cells + halo with their own boxes: id order)
-    if (mode == BRICK_FWD || mode == BRICK_FWD_AUX || mode == BRICK_VOLGRAD || mode == BRICK_CHANNELS ||
-        mode == BRICK_CHANNELS_WORDS || mode == BRICK_CHANNELS_AUX || mode == BRICK_CHANNELS_VOLGRAD)
-        order_bricks(p, BRICK, BRICK, BRICK, bg.ny, bg.nz, n_bricks, n_cu_dev, st);
-    // (the marcher's volume gradient: owner bricks = the plain grid; a brick's walks are long
-    // whatever the pose count)
-    if (mode == BRICK_TRI_VOLGRAD) order_bricks(p, BRICK, BRICK, BRICK, bg.ny, bg.nz, n_bricks, n_cu_dev, st, false, 1);
-    const dim3 grid(n_bricks < n_cu_dev ? n_bricks : n_cu_dev), block(kBrickThreads);
-    if (mode == BRICK_TRI_FWD)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_TRI_FWD>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_TRI_FWD_AUX)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_TRI_FWD_AUX>, grid, block, lds, st, p, out,
-                           aux);
-    else if (mode == BRICK_TRI_VOLGRAD)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_TRI_VOLGRAD>, grid, block, lds, st, p, out,
-                           aux);
-    else if (mode == BRICK_FWD)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_FWD>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_FWD_AUX)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_FWD_AUX>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_CHANNELS)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_CHANNELS>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_CHANNELS_WORDS)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_CHANNELS_WORDS>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_CHANNELS_AUX)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_CHANNELS_AUX>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_TRI_CHANNELS)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_TRI_CHANNELS>, grid, block, lds, st, p, out, aux);
-    else if (mode == BRICK_TRI_CHANNELS_AUX)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_TRI_CHANNELS_AUX>, grid, block, lds, st, p, out,
-                           aux);
-    else if (mode == BRICK_CHANNELS_VOLGRAD)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_CHANNELS_VOLGRAD>, grid, block, lds, st, p, out,
-                           aux);
-    else if (mode == BRICK_TRI_CHANNELS_VOLGRAD)
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_TRI_CHANNELS_VOLGRAD>, grid, block, lds, st, p,
-                           out, aux);
-    else
-        hipLaunchKernelGGL(siddon_brick_kernel<BRICK_VOLGRAD>, grid, block, lds, st, p, out, aux);
-    return finish(who);
+    if (m->order_min_poses)
+        order_bricks(p, BRICK, BRICK, BRICK, bg.ny, bg.nz, n_bricks, n_cu, l.st, false, m->order_min_poses);
+    const dim3 grid(n_bricks < n_cu ? n_bricks : n_cu), block(kBrickThreads);
+    hipLaunchKernelGGL(m->kernel, grid, block, lds, l.st, p, l.out, l.aux);
+    return finish(l.who);
 }
 
 }  // namespace ddrr_brick
@@ -1320,6 +1284,37 @@ int ddrr_brick_profile_read(unsigned long long *host16) {
 }
 #endif
 
+// Argument rules that the *_bricks entries share (every entry applies them in its own order, before
+// its first HIP call), and their two ways of zeroing a buffer.
+static int check_detector(int det_h, int det_w) {
+    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
+    return 0;
+}
+// (per_ray_entry: the entry that takes what one channel launch on the bricks cannot)
+static int check_channel_cap(int B, int C, int N, const char *per_ray_entry) {
+    if ((long)B * C * N < (1L << 30) && N < (1 << 22)) return 0;
+    char msg[256];
+    snprintf(msg, sizeof(msg), "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
+                               "on the bricks: split the pose batch or use %s", per_ray_entry);
+    return fail(-1, msg);
+}
+static int check_n_points(int n_points) {
+    if (n_points < 2) return fail(-1, "n_points must be >= 2");
+    return 0;
+}
+static int check_alpha_range(const float *alphamin, const float *alphamax) {
+    if (!alphamin || !alphamax) return fail(-1, "null alphamin / alphamax");
+    return 0;
+}
+static int zero_floats(float *buf, size_t n, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(buf, 0, sizeof(float) * n, st);
+    return e == hipSuccess ? 0 : fail_hip(e, "hipMemsetAsync");
+}
+// (no pose: nothing contributes, the volume gradient is zero)
+static int zero_volume_gradient(float *g_volume, int dx, int dy, int dz, hipStream_t st) {
+    return zero_floats(g_volume, (size_t)dx * dy * dz, st);
+}
+
 static int siddon_forward_bricks_impl(const float *volume, int dx, int dy, int dz, const float *source,
                                       const float *target, const float *img, int B, int det_h,
                                       int det_w, float voxel_shift, float eps, float *out, float *aux,
@@ -1329,7 +1324,7 @@ static int siddon_forward_bricks_impl(const float *volume, int dx, int dy, int d
     const int N = det_h * det_w;
     if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
     if (!out && !aux) return fail(-1, "null out pointer");  // (the record alone: ddrr_siddon_ncc_forward forms the image)
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
+    if (int rc = check_detector(det_h, det_w)) return rc;
     if (!(record_vmax >= 0.f)) return fail(-1, "record_vmax must be >= 0");
     if (brick_storage != DDRR_BRICKS_F32 && brick_storage != DDRR_BRICKS_Q16 &&
         brick_storage != DDRR_BRICKS_Q16_PACKED)
@@ -1341,29 +1336,32 @@ static int siddon_forward_bricks_impl(const float *volume, int dx, int dy, int d
     const long R = (long)B * N;
     // (DDRR_BRICKS_CLEARED: the record / image and the brick counter are zero already)
     const bool cleared = (ranges_valid & DDRR_BRICKS_CLEARED) != 0;
-    ranges_valid &= 1;
     const bool packed = aux && record_vmax > 0.f;
     // (the packed record's planes 5, 6 are written by record_prepare_kernel)
     const size_t fill = !aux ? (size_t)R : (packed ? (size_t)R * 5 : (size_t)rec_blocked_floats(R));
+    BrickLaunch l{volume, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st, launch_ws,
+                  "ddrr_siddon_forward_bricks"};
+    l.out = out;
+    l.aux = aux;
+    l.pix_mask = pixel_mask;
     // (the packed record's preparation writes behind the zeros: cleared here; else with the brick
     // counter, by one launch: launch_fwd_bricks)
-    float rec_q = 0.f;
     if (packed) {
-        const hipError_t e = cleared ? hipSuccess : hipMemsetAsync(aux, 0, sizeof(float) * fill, st);
-        if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-        rec_q = record_scale(record_vmax, Dims{dx, dy, dz});
+        if (!cleared)
+            if (int rc = zero_floats(aux, fill, st)) return rc;
+        l.rec_q = record_scale(record_vmax, Dims{dx, dy, dz});
         hipLaunchKernelGGL(record_prepare_kernel, dim3((unsigned)((R + kBlock - 1) / kBlock)),
                            dim3(kBlock), 0, st, source, target, R, N, Dims{dx, dy, dz}, voxel_shift,
-                           eps, rec_q, aux);
+                           eps, l.rec_q, aux);
     }
-    const int packed_bricks = brick_storage == DDRR_BRICKS_Q16_PACKED;
-    if (int rc = launch_fwd_bricks(packed_bricks ? DDRR_BRICKS_Q16 : brick_storage, packed_bricks,
-                                   brick_ranges, ranges_valid, volume, dx, dy, dz,
-                                   source, target, img, B, det_h, det_w, voxel_shift, eps, out, aux,
-                                   rec_q, st, launch_ws, "ddrr_siddon_forward_bricks",
-                                   packed || cleared ? nullptr : (aux ? aux : out),
-                                   cleared ? -1 : (packed ? 0 : (long)fill), pixel_mask))
-        return rc;
+    FwdStorage fs;
+    fs.packed = brick_storage == DDRR_BRICKS_Q16_PACKED;
+    fs.variant = fs.packed ? DDRR_BRICKS_Q16 : brick_storage;
+    fs.brick_ranges = brick_ranges;
+    fs.ranges_valid = ranges_valid & 1;
+    fs.clear = packed || cleared ? nullptr : (aux ? aux : out);
+    fs.clear_n = cleared ? -1 : (packed ? 0 : (long)fill);
+    if (int rc = launch_fwd_bricks(l, fs)) return rc;
     if (!aux) return 0;
     if (out)
         hipLaunchKernelGGL(siddon_out_from_record_kernel, dim3((unsigned)((R + kBlock - 1) / kBlock)),
@@ -1414,17 +1412,17 @@ int ddrr_siddon_forward_channels_bricks(const float *volume, const unsigned char
                               "ddrr_siddon_forward_channels_bricks (mask_to_channels)"))
         return rc;
     if (!labels || !out || C < 1) return fail(-1, "null labels/out or C < 1");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_siddon_forward_channels");
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_siddon_forward_channels")) return rc;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * C * N, st);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-    return launch_bricks(BRICK_CHANNELS, volume, dx, dy, dz, source, target, img, nullptr, B, det_h,
-                         det_w, voxel_shift, eps, out, nullptr, nullptr, st, launch_ws,
-                         "ddrr_siddon_forward_channels_bricks", 0, nullptr, nullptr, 0.f, labels, C);
+    if (int rc = zero_floats(out, (size_t)B * C * N, st)) return rc;
+    BrickLaunch l{volume, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st, launch_ws,
+                  "ddrr_siddon_forward_channels_bricks"};
+    l.out = out;
+    l.labels = labels;
+    l.n_channels = C;
+    return launch_bricks(BRICK_CHANNELS, l);
 }
 
 // The channel render's staged words -- value rounded to a 16-bit mantissa | label, labels without a
@@ -1498,17 +1496,16 @@ int ddrr_siddon_forward_channels_bricks_words(const float *words, int dx, int dy
                               "ddrr_siddon_forward_channels_bricks_words (mask_to_channels)"))
         return rc;
     if (!out || C < 1) return fail(-1, "null out or C < 1");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_siddon_forward_channels");
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_siddon_forward_channels")) return rc;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * C * N, st);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-    return launch_bricks(BRICK_CHANNELS_WORDS, words, dx, dy, dz, source, target, img, nullptr, B, det_h,
-                         det_w, voxel_shift, eps, out, nullptr, nullptr, st, launch_ws,
-                         "ddrr_siddon_forward_channels_bricks_words", 0, nullptr, nullptr, 0.f, nullptr, C);
+    if (int rc = zero_floats(out, (size_t)B * C * N, st)) return rc;
+    BrickLaunch l{words, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st, launch_ws,
+                  "ddrr_siddon_forward_channels_bricks_words"};
+    l.out = out;
+    l.n_channels = C;
+    return launch_bricks(BRICK_CHANNELS_WORDS, l);
 }
 
 int ddrr_siddon_backward_channels_bricks(const float *volume, const unsigned char *labels, int dx,
@@ -1521,17 +1518,18 @@ int ddrr_siddon_backward_channels_bricks(const float *volume, const unsigned cha
                               "ddrr_siddon_backward_channels_bricks (mask_to_channels)"))
         return rc;
     if (!labels || !grad_out || !aux || C < 1) return fail(-1, "null labels/grad_out/aux or C < 1");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_siddon_backward_channels");
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_siddon_backward_channels")) return rc;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(aux, 0, sizeof(float) * (size_t)rec_blocked_floats((long)B * N), st);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-    return launch_bricks(BRICK_CHANNELS_AUX, volume, dx, dy, dz, source, target, nullptr, grad_out, B,
-                         det_h, det_w, voxel_shift, eps, nullptr, aux, nullptr, st, launch_ws,
-                         "ddrr_siddon_backward_channels_bricks", 0, nullptr, nullptr, 0.f, labels, C);
+    if (int rc = zero_floats(aux, (size_t)rec_blocked_floats((long)B * N), st)) return rc;
+    BrickLaunch l{volume, dx, dy, dz, source, target, /*img=*/nullptr, B, det_h, det_w, voxel_shift, eps, st,
+                  launch_ws, "ddrr_siddon_backward_channels_bricks"};
+    l.grad_out = grad_out;
+    l.aux = aux;
+    l.labels = labels;
+    l.n_channels = C;
+    return launch_bricks(BRICK_CHANNELS_AUX, l);
 }
 
 int ddrr_trilinear_forward_channels_bricks(const float *volume, const unsigned char *labels,
@@ -1546,20 +1544,22 @@ int ddrr_trilinear_forward_channels_bricks(const float *volume, const unsigned c
                               "ddrr_trilinear_forward_channels_bricks (mask_to_channels)"))
         return rc;
     if (!labels || !out || C < 1) return fail(-1, "null labels/out or C < 1");
-    if (!alphamin || !alphamax) return fail(-1, "null alphamin / alphamax");
-    if (n_points < 2) return fail(-1, "n_points must be >= 2");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_trilinear_forward_channels");
+    if (int rc = check_alpha_range(alphamin, alphamax)) return rc;
+    if (int rc = check_n_points(n_points)) return rc;
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_trilinear_forward_channels")) return rc;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * C * N, st);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-    return launch_bricks(BRICK_TRI_CHANNELS, volume, dx, dy, dz, source, target, img, nullptr, B,
-                         det_h, det_w, voxel_shift, eps, out, nullptr, nullptr, st, launch_ws,
-                         "ddrr_trilinear_forward_channels_bricks", n_points, alphamin, alphamax, 0.f,
-                         labels, C);
+    if (int rc = zero_floats(out, (size_t)B * C * N, st)) return rc;
+    BrickLaunch l{volume, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st, launch_ws,
+                  "ddrr_trilinear_forward_channels_bricks"};
+    l.out = out;
+    l.n_points = n_points;
+    l.amin = alphamin;
+    l.amax = alphamax;
+    l.labels = labels;
+    l.n_channels = C;
+    return launch_bricks(BRICK_TRI_CHANNELS, l);
 }
 
 int ddrr_trilinear_backward_channels_bricks(const float *volume, const unsigned char *labels,
@@ -1574,20 +1574,23 @@ int ddrr_trilinear_backward_channels_bricks(const float *volume, const unsigned 
                               "ddrr_trilinear_backward_channels_bricks (mask_to_channels)"))
         return rc;
     if (!labels || !grad_out || !aux || C < 1) return fail(-1, "null labels/grad_out/aux or C < 1");
-    if (!alphamin || !alphamax) return fail(-1, "null alphamin / alphamax");
-    if (n_points < 2) return fail(-1, "n_points must be >= 2");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_trilinear_backward_channels");
+    if (int rc = check_alpha_range(alphamin, alphamax)) return rc;
+    if (int rc = check_n_points(n_points)) return rc;
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_trilinear_backward_channels")) return rc;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(aux, 0, sizeof(float) * (size_t)B * N * DDRR_TRI_AUX_PLANES, st);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-    return launch_bricks(BRICK_TRI_CHANNELS_AUX, volume, dx, dy, dz, source, target, nullptr,
-                         grad_out, B, det_h, det_w, voxel_shift, eps, nullptr, aux, nullptr, st,
-                         launch_ws, "ddrr_trilinear_backward_channels_bricks", n_points, alphamin,
-                         alphamax, 0.f, labels, C);
+    if (int rc = zero_floats(aux, (size_t)B * N * DDRR_TRI_AUX_PLANES, st)) return rc;
+    BrickLaunch l{volume, dx, dy, dz, source, target, /*img=*/nullptr, B, det_h, det_w, voxel_shift, eps, st,
+                  launch_ws, "ddrr_trilinear_backward_channels_bricks"};
+    l.grad_out = grad_out;
+    l.aux = aux;
+    l.n_points = n_points;
+    l.amin = alphamin;
+    l.amax = alphamax;
+    l.labels = labels;
+    l.n_channels = C;
+    return launch_bricks(BRICK_TRI_CHANNELS_AUX, l);
 }
 
 int ddrr_siddon_backward_channels_volume_bricks(const unsigned char *labels, int dx, int dy, int dz,
@@ -1602,19 +1605,17 @@ int ddrr_siddon_backward_channels_volume_bricks(const unsigned char *labels, int
     if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N,
                               "ddrr_siddon_backward_channels_volume_bricks (mask_to_channels)"))
         return rc;
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_siddon_backward_channels");
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_siddon_backward_channels")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {  // nothing contributes: the gradient is zero
-        hipError_t e = hipMemsetAsync(g_volume, 0, sizeof(float) * (size_t)dx * dy * dz, st);
-        return e == hipSuccess ? 0 : fail_hip(e, "hipMemsetAsync");
-    }
-    return launch_bricks(BRICK_CHANNELS_VOLGRAD, nullptr, dx, dy, dz, source, target, img, grad_out,
-                         B, det_h, det_w, voxel_shift, eps, nullptr, nullptr, g_volume, st, launch_ws,
-                         "ddrr_siddon_backward_channels_volume_bricks", 0, nullptr, nullptr, 0.f,
-                         labels, C);
+    if (B == 0) return zero_volume_gradient(g_volume, dx, dy, dz, st);
+    BrickLaunch l{/*volume=*/nullptr, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st,
+                  launch_ws, "ddrr_siddon_backward_channels_volume_bricks"};
+    l.grad_out = grad_out;
+    l.g_volume = g_volume;
+    l.labels = labels;
+    l.n_channels = C;
+    return launch_bricks(BRICK_CHANNELS_VOLGRAD, l);
 }
 
 int ddrr_siddon_backward_volume_bricks(int dx, int dy, int dz, const float *source,
@@ -1625,15 +1626,14 @@ int ddrr_siddon_backward_volume_bricks(int dx, int dy, int dz, const float *sour
     const int N = det_h * det_w;
     if (!g_volume || !grad_out) return fail(-1, "null grad_out / g_volume");
     if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
+    if (int rc = check_detector(det_h, det_w)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {  // nothing contributes: the gradient is zero
-        hipError_t e = hipMemsetAsync(g_volume, 0, sizeof(float) * (size_t)dx * dy * dz, st);
-        return e == hipSuccess ? 0 : fail_hip(e, "hipMemsetAsync");
-    }
-    return launch_bricks(BRICK_VOLGRAD, nullptr, dx, dy, dz, source, target, img, grad_out, B,
-                         det_h, det_w, voxel_shift, eps, nullptr, nullptr, g_volume, st, launch_ws,
-                         "ddrr_siddon_backward_volume_bricks");
+    if (B == 0) return zero_volume_gradient(g_volume, dx, dy, dz, st);
+    BrickLaunch l{/*volume=*/nullptr, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st,
+                  launch_ws, "ddrr_siddon_backward_volume_bricks"};
+    l.grad_out = grad_out;
+    l.g_volume = g_volume;
+    return launch_bricks(BRICK_VOLGRAD, l);
 }
 
 int ddrr_trilinear_forward_bricks(const float *volume, int dx, int dy, int dz,
@@ -1644,22 +1644,21 @@ int ddrr_trilinear_forward_bricks(const float *volume, int dx, int dy, int dz,
     const int N = det_h * det_w;
     if (int rc = check_common(volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
     if (!out || !alphamin || !alphamax) return fail(-1, "null out / alphamin / alphamax");
-    if (n_points < 2) return fail(-1, "n_points must be >= 2");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
+    if (int rc = check_n_points(n_points)) return rc;
+    if (int rc = check_detector(det_h, det_w)) return rc;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const long R = (long)B * N;
-    hipError_t e = hipMemsetAsync(aux ? aux : out, 0,
-                                  sizeof(float) * (size_t)R * (aux ? DDRR_TRI_AUX_PLANES : 1), st);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-    if (!aux)
-        return launch_bricks(BRICK_TRI_FWD, volume, dx, dy, dz, source, target, img, nullptr, B,
-                             det_h, det_w, voxel_shift, eps, out, nullptr, nullptr, st, launch_ws,
-                             "ddrr_trilinear_forward_bricks", n_points, alphamin, alphamax);
-    if (int rc = launch_bricks(BRICK_TRI_FWD_AUX, volume, dx, dy, dz, source, target, img, nullptr,
-                               B, det_h, det_w, voxel_shift, eps, out, aux, nullptr, st, launch_ws,
-                               "ddrr_trilinear_forward_bricks", n_points, alphamin, alphamax))
-        return rc;
+    if (int rc = zero_floats(aux ? aux : out, (size_t)R * (aux ? DDRR_TRI_AUX_PLANES : 1), st)) return rc;
+    BrickLaunch l{volume, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st, launch_ws,
+                  "ddrr_trilinear_forward_bricks"};
+    l.out = out;
+    l.aux = aux;
+    l.n_points = n_points;
+    l.amin = alphamin;
+    l.amax = alphamax;
+    if (!aux) return launch_bricks(BRICK_TRI_FWD, l);
+    if (int rc = launch_bricks(BRICK_TRI_FWD_AUX, l)) return rc;
     hipLaunchKernelGGL(tri_out_from_record_kernel, dim3((unsigned)((R + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, st, aux, img, R, n_points, alphamin, alphamax, out);
     return finish("ddrr_trilinear_forward_bricks");
@@ -1695,20 +1694,21 @@ int ddrr_trilinear_backward_channels_volume_bricks(const unsigned char *labels, 
     if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N,
                               "ddrr_trilinear_backward_channels_volume_bricks (mask_to_channels)"))
         return rc;
-    if (n_points < 2) return fail(-1, "n_points must be >= 2");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
-    if ((long)B * C * N >= (1L << 30) || N >= (1 << 22))
-        return fail(-1, "B * C * N must stay below 2^30 (and N below 2^22) for one channel launch "
-                        "on the bricks: split the pose batch or use ddrr_trilinear_backward_channels");
+    if (int rc = check_n_points(n_points)) return rc;
+    if (int rc = check_detector(det_h, det_w)) return rc;
+    if (int rc = check_channel_cap(B, C, N, "ddrr_trilinear_backward_channels")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {
-        hipError_t e = hipMemsetAsync(g_volume, 0, sizeof(float) * (size_t)dx * dy * dz, st);
-        return e == hipSuccess ? 0 : fail_hip(e, "hipMemsetAsync");
-    }
-    return launch_bricks(BRICK_TRI_CHANNELS_VOLGRAD, nullptr, dx, dy, dz, source, target, img,
-                         grad_out, B, det_h, det_w, voxel_shift, eps, nullptr, nullptr, g_volume, st,
-                         launch_ws, "ddrr_trilinear_backward_channels_volume_bricks", n_points, alphamin,
-                         alphamax, 0.f, labels, C);
+    if (B == 0) return zero_volume_gradient(g_volume, dx, dy, dz, st);
+    BrickLaunch l{/*volume=*/nullptr, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st,
+                  launch_ws, "ddrr_trilinear_backward_channels_volume_bricks"};
+    l.grad_out = grad_out;
+    l.g_volume = g_volume;
+    l.n_points = n_points;
+    l.amin = alphamin;
+    l.amax = alphamax;
+    l.labels = labels;
+    l.n_channels = C;
+    return launch_bricks(BRICK_TRI_CHANNELS_VOLGRAD, l);
 }
 
 int ddrr_trilinear_backward_volume_bricks(int dx, int dy, int dz, const float *source,
@@ -1721,16 +1721,18 @@ int ddrr_trilinear_backward_volume_bricks(int dx, int dy, int dz, const float *s
     if (!g_volume || !grad_out || !alphamin || !alphamax)
         return fail(-1, "null grad_out / g_volume / alphamin / alphamax");
     if (int rc = check_common(g_volume, dx, dy, dz, source, 1, target, B, N, nullptr)) return rc;
-    if (n_points < 2) return fail(-1, "n_points must be >= 2");
-    if (det_h < 2 || det_w < 2) return fail(-1, "the brick path needs a detector of at least 2x2");
+    if (int rc = check_n_points(n_points)) return rc;
+    if (int rc = check_detector(det_h, det_w)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {
-        hipError_t e = hipMemsetAsync(g_volume, 0, sizeof(float) * (size_t)dx * dy * dz, st);
-        return e == hipSuccess ? 0 : fail_hip(e, "hipMemsetAsync");
-    }
-    return launch_bricks(BRICK_TRI_VOLGRAD, nullptr, dx, dy, dz, source, target, img, grad_out, B,
-                         det_h, det_w, voxel_shift, eps, nullptr, nullptr, g_volume, st, launch_ws,
-                         "ddrr_trilinear_backward_volume_bricks", n_points, alphamin, alphamax);
+    if (B == 0) return zero_volume_gradient(g_volume, dx, dy, dz, st);
+    BrickLaunch l{/*volume=*/nullptr, dx, dy, dz, source, target, img, B, det_h, det_w, voxel_shift, eps, st,
+                  launch_ws, "ddrr_trilinear_backward_volume_bricks"};
+    l.grad_out = grad_out;
+    l.g_volume = g_volume;
+    l.n_points = n_points;
+    l.amin = alphamin;
+    l.amax = alphamax;
+    return launch_bricks(BRICK_TRI_VOLGRAD, l);
 }
 
 }  // extern "C"

@@ -17,11 +17,11 @@
 //     (profiles/r03, tools builds keep them as variants): two 512-thread workgroups per CU on
 //     32^3 16-bit bricks or on 32 x 32 x 16 fp32 half bricks (their barrier waits halve, their
 //     staging time doubles: no gain), anisotropic fp32 bricks 16 x 64 x 32 ... (3-8 % slower on
-//     mixed poses), workgroup-shared rings of 12 length classes (see below).
+//     mixed poses).  Workgroup-shared rings of 12 length classes were measured too and are no
+//     longer in the tree: profiles/r03/NOTES.md section 3.1 has the result.
 // Reference: diffdrr/renderers.py:34-76, 94-113 (Siddon.forward, mask=None, sum, nearest).
 #include "runtime.h"
 
-#include <mutex>
 #include "siddon_core.h"
 #include "brick_core.h"
 #include "brick_walk.h"
@@ -969,286 +969,6 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
 #endif
 }
 
-// ------------------------------------------------------------------ shared length-class rings
-// The same kernel with the hit queues SHARED by the workgroup: NCLS length classes (equal
-// width in estimated crossings) instead of 3, each a ring of CAP entries in LDS with two
-// counters: tail[c], tickets handed out, and head[c], batches of 64 taken -- in order.
-//   * A wave's push reserves the tickets of all its classes with one LDS atomic (lane c adds
-//     the unit's count of class c to tail[c]; with the float record the first hit of each run of
-//     8 pixels reserves for its run, so that runs stay together) and stores ticket t's entry in
-//     slot t mod CAP -- once head[c] says the slot's previous ticket, t - CAP, has been taken.
-//   * The push whose reservation completes a batch (tickets 64 k .. 64 k + 63) owns it: when
-//     head[c] == k it waits for the 64 slots to be written, takes them (reads, marks EMPTY),
-//     sets head[c] = k + 1 and walks them.  A push takes ALL the batches it owns before it walks
-//     the first one, so that nobody waits for a walk.
-//   * Every wait is for a push that reserved EARLIER (a writer for the owner of a batch CAP
-//     tickets back; an owner for the writers of its batch and the owner of the batch before):
-//     the oldest unfinished push never waits, so there is no cycle, whatever CAP.  The spins are
-//     bounded all the same (kSqSpinCap): a logic error ends in a NaN image, not a hang.
-//   * When the units of the last chunk are gone the waves meet at a barrier; what is left (< 64
-//     per class) is handed out 64 at a time, longest class first.
-// With 16 waves feeding one set of rings a class fills 16x faster than a per-wave queue: twelve
-// classes cost < 12 partial batches per brick (48 with the 3 per-wave queues), and a batch
-// holds rays within one class width of each other.
-constexpr unsigned kSqEmpty = 0xffffffffu;
-constexpr int kSqSpinCap = 1 << 22;
-
-template <int NCLS_, class C>
-struct SqCfg {
-    static constexpr int NCLS = NCLS_;
-    // ring entries per class: the power of two that fits the per-wave queues' LDS
-    static constexpr int ROOM = C::WAVES * kBuckets * kQueueCap / NCLS;
-    static constexpr int CAP = ROOM >= 1024 ? 1024 : (ROOM >= 512 ? 512 : (ROOM >= 256 ? 256 : 128));
-    static_assert(ROOM >= 128, "ring too small");
-    // (the row table and the control words lie behind the rings exactly as behind the queues)
-    static constexpr int LDS = C::LDS + 64 + 8 * NCLS;
-};
-
-template <bool AUX, class C, int NCLS>
-__global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void
-siddon_fwd_brick_sq_kernel(BrickArgs p, float *__restrict__ out, float *__restrict__ aux) {
-    using S = SqCfg<NCLS, C>;
-    constexpr int CAP = S::CAP;
-    static_assert(NCLS * 63 <= 64 * C::WAVES, "the leftovers of a brick: one batch per wave at most");
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    unsigned char *brick = smem_raw;
-    unsigned *ring = reinterpret_cast<unsigned *>(smem_raw + C::BRICK_BYTES);  // [NCLS][CAP]
-    FwdRow *rows = reinterpret_cast<FwdRow *>(ring + C::WAVES * kBuckets * kQueueCap);
-    int *counter = reinterpret_cast<int *>(rows + C::CHUNK);  // [0] unit, [1] brick, [2] non-zero
-    volatile int *tail = counter + 4;                         // [NCLS] tickets handed out
-    volatile int *head = tail + NCLS;                         // [NCLS] batches taken (in order)
-    volatile int *fault = head + NCLS;                        // a spin ran into its bound
-
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nbx = (p.D.x + C::BX - 1) / C::BX, nby = (p.D.y + C::BY - 1) / C::BY;
-    const int nbz = (p.D.z + C::BZ - 1) / C::BZ;
-    const int n_bricks = nbx * nby * nbz;
-    const int N = p.det_h * p.det_w;
-    const unsigned pix_mask = (1u << p.pix_bits) - 1u;
-    const int n_chunks = (p.B + C::CHUNK - 1) / C::CHUNK;
-    const int chunk = (p.B + n_chunks - 1) / n_chunks;
-    const unsigned lds_base = LdsAbsFetch::base_of(reinterpret_cast<const float *>(brick));
-    const bool GROUPED = AUX && p.rec_q == 0.f && !(p.dbg & 8);
-    const float inv_width = 1.0f / p.t1;  // class = estimated crossings / width
-
-    for (int i = tid; i < NCLS * CAP; i += C::THREADS) ring[i] = kSqEmpty;
-    if (tid == 0) *fault = 0;
-
-    BrickProf prof;
-#if defined(DDRR_BRICK_PROFILE)
-    prof.start();
-#endif
-    // take the 64 entries of batch k of class c (lane l: ticket 64 k + l); in order
-    auto take_batch = [&](int c, int k) -> unsigned {
-        int spin = 0;
-        while (head[c] != k && ++spin < kSqSpinCap) {
-        }
-        volatile unsigned *slot = ring + c * CAP + ((64 * k + lane) & (CAP - 1));
-        unsigned e = *slot;
-        while (__ballot(e == kSqEmpty) && ++spin < kSqSpinCap) e = *slot;
-        if (spin >= kSqSpinCap) *fault = 1;
-        *slot = kSqEmpty;
-        wave_fence();
-        if (lane == 0) head[c] = k + 1;  // (LDS operations of a wave are performed in order)
-        return e;
-    };
-    auto walk_entries = [&](unsigned e, const StepGeom &SG, const Q16Range &range) {
-        DDRR_PROF(PROF_POP);
-        DDRR_PROF_COUNT(PROF_N_BATCH, 1);
-        fwd_item<AUX, C>(p, lds_base, SG, range, e != kSqEmpty, e >> p.pix_bits, e & pix_mask, out,
-                         aux, prof);
-    };
-
-    for (;;) {
-        __syncthreads();  // every wave is done with the previous brick's LDS
-        DDRR_PROF(PROF_BARRIER);
-        if (tid == 0) {
-            counter[1] = atomicAdd(p.work, 1);
-            counter[2] = 0;
-        }
-        if (tid < NCLS) {
-            tail[tid] = 0;
-            head[tid] = 0;
-        }
-        __syncthreads();
-        const int brick_id = counter[1];
-        if (brick_id >= n_bricks) break;
-        DDRR_PROF(PROF_CLAIM);
-        const Box box = cfg_brick_box<C>(p.D, nby, nbz, brick_id);
-        const BoxF cells = boxf(box);
-        StepGeom SG;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            SG.lof[a] = (float)box.lo[a];
-            SG.hif[a] = (float)box.hi[a];
-        }
-        SG.strideb[0] = bits_as_float((unsigned)C::SX);
-        SG.strideb[1] = bits_as_float((unsigned)C::SY);
-        SG.strideb[2] = bits_as_float((unsigned)C::ES);
-        bool brick_empty = false;
-        Q16Range range = {0.f, 0.f, 0.f};
-
-        for (int ch = 0; ch < n_chunks; ++ch) {
-            const int b0 = ch * chunk;
-            const int nb = p.B - b0 < chunk ? p.B - b0 : chunk;
-            const bool last_chunk = ch == n_chunks - 1;
-            if (ch > 0) __syncthreads();  // previous chunk's table no longer in use
-            if (tid < nb) {
-                const PoseGrid pg = pose_grid(p.source + (long)(b0 + tid) * 3,
-                                              p.target + (long)(b0 + tid) * N * 3, p.det_h, p.det_w);
-                PixBox pb = project_brick_grid(pg, p.det_h, p.det_w, cells, p.shift);
-                if (GROUPED) pb = align_pixbox_rows(pb, p.det_w);
-                rows[tid] = fwd_row(brick_row(pg, pb, cells, p.shift, p.eps, 0.f));
-            }
-            if (tid == 0) counter[0] = 0;
-            DDRR_PROF(PROF_ROWS);
-            if (ch == 0) fwd_stage_brick<C>(p, brick, box, brick_id, tid, range, brick_empty, counter);
-            DDRR_PROF(PROF_STORE);
-            __syncthreads();
-            if (!C::Q16 && ch == 0) brick_empty = counter[2] == 0;
-            int incl = lane < nb ? (rows[lane].count + 63) >> 6 : 0;
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) {
-                const int up = __shfl_up(incl, o, 64);
-                incl += lane >= o ? up : 0;
-            }
-            const int units = brick_empty ? 0 : __builtin_amdgcn_readlane(incl, 31);
-            int cur = 0, cur_lo = 0, cur_hi = __builtin_amdgcn_readlane(incl, 0);
-            DDRR_PROF(PROF_STAGE);
-            for (;;) {
-                int u = 0;
-                if (lane == 0) u = atomicAdd(&counter[0], 1);
-                u = uni(u);
-                if (u >= units) break;  // no unit left in this chunk
-                while (u >= cur_hi) {   // units arrive in increasing order: forward cursor
-                    ++cur;
-                    cur_lo = cur_hi;
-                    cur_hi = __builtin_amdgcn_readlane(incl, uni(cur));
-                }
-                const BrickRow r = brick_row_of(rows[cur]);
-                DDRR_PROF(PROF_PULL);
-                DDRR_PROF_COUNT(PROF_N_UNITS, 1);
-                const int local = (u - cur_lo) * 64 + lane;
-                const bool valid = local < uni(r.count);
-                int pix = 0;
-                float n_est = 0.f;
-                const bool hit = valid && brick_candidate(r, local, p.det_w, pix, n_est);
-                float n_grp = hit ? n_est : 0.f;
-                if (GROUPED) {  // float record: classes per run of 8 adjacent pixels (bricks.hip)
-                    n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                        0, __builtin_bit_cast(int, n_grp), 0xB1, 0xf, 0xf, true)));   // lane ^ 1
-                    n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                        0, __builtin_bit_cast(int, n_grp), 0x4E, 0xf, 0xf, true)));   // lane ^ 2
-                    n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                        0, __builtin_bit_cast(int, n_grp), 0x141, 0xf, 0xf, true)));  // 7 - lane
-                }
-                int cls = (int)(n_grp * inv_width);
-                cls = cls < NCLS - 1 ? cls : NCLS - 1;
-                cls = cls > 0 ? cls : 0;
-                const unsigned long long hits = __ballot(hit);
-                DDRR_PROF_COUNT(PROF_N_HITS, __popcll(hits));
-                // Tickets: `own_cls` / `own_batch` on the lanes whose reservation completed a batch
-                int ticket = 0, own_cls = 0, own_batch = 0;
-                bool owns = false;
-                if (!GROUPED) {
-                    // per class present in the unit: its hits' ranks, its count on lane c
-                    int cnt_mine = 0, rank = 0;
-                    unsigned long long rem = hits;
-                    while (rem) {
-                        const int c = __builtin_amdgcn_readlane(cls, __ffsll((long long)rem) - 1);
-                        const unsigned long long m = __ballot(hit && cls == c);
-                        cnt_mine = lane == c ? (int)__popcll(m) : cnt_mine;
-                        rank = cls == c ? lane_rank(m) : rank;
-                        rem &= ~m;
-                    }
-                    int first = 0;  // one LDS atomic reserves for all classes: lane c, class c
-                    if (lane < NCLS && cnt_mine > 0) first = atomicAdd((int *)&tail[lane], cnt_mine);
-                    owns = lane < NCLS && cnt_mine > 0 && ((first + cnt_mine) >> 6) != (first >> 6);
-                    own_cls = lane;
-                    own_batch = first >> 6;
-                    ticket = __shfl(first, cls, 64) + rank;
-                } else {
-                    // float record: the hits of a run of 8 pixels share a class and stay together
-                    const unsigned half = lane < 32 ? (unsigned)hits : (unsigned)(hits >> 32);
-                    const unsigned grp = (half >> (lane & 24)) & 0xffu;  // hits of my run of 8
-                    const int n_run = __popc(grp), before = __popc(grp & ((1u << (lane & 7)) - 1u));
-                    const bool leader = hit && before == 0;
-                    int first = 0;
-                    if (leader) first = atomicAdd((int *)&tail[cls], n_run);
-                    owns = leader && ((first + n_run) >> 6) != (first >> 6);
-                    own_cls = cls;
-                    own_batch = first >> 6;
-                    const int lead_lane = (lane & ~7) + (__ffs(grp | 0x100u) - 1);
-                    ticket = __shfl(first, lead_lane & 63, 64) + before;
-                }
-                if (hit) {
-                    // slot t mod CAP is free once batch (t - CAP) / 64 has been taken
-                    const int need = (ticket >> 6) - CAP / 64 + 1;
-                    int spin = 0;
-                    while (head[cls] < need && ++spin < kSqSpinCap) {
-                    }
-                    if (spin >= kSqSpinCap) *fault = 1;
-                    const_cast<volatile unsigned *>(ring)[cls * CAP + (ticket & (CAP - 1))] =
-                        ((unsigned)(b0 + cur) << p.pix_bits) | (unsigned)pix;
-                }
-                wave_fence();
-                DDRR_PROF(PROF_PHASE_A);
-                // the batches this push completed are this wave's: take them all, then walk them
-                unsigned long long own = __ballot(owns);
-                while (own) {
-                    unsigned e[4];
-                    int n_own = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        e[j] = kSqEmpty;
-                        if (own) {
-                            const int l = __ffsll((long long)own) - 1;
-                            own &= own - 1;
-                            e[j] = take_batch(__builtin_amdgcn_readlane(own_cls, l),
-                                              __builtin_amdgcn_readlane(own_batch, l));
-                            n_own = j + 1;
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (j < n_own) walk_entries(e[j], SG, range);
-                }
-            }
-            if (!last_chunk) continue;
-            // every push of this brick has been made: hand out what is left, longest class first
-            __syncthreads();
-            DDRR_PROF(PROF_BARRIER);
-            int left_before = 0;  // leftovers of the classes above c
-            unsigned e = kSqEmpty;
-            const int pos = 64 * wave + lane;
-#pragma unroll 1
-            for (int c = NCLS - 1; c >= 0; --c) {
-                const int tl = tail[c], left = tl & 63;  // (every complete batch has been taken)
-                const int i = pos - left_before;
-                if (i >= 0 && i < left) {
-                    unsigned *slot = ring + c * CAP + ((tl - left + i) & (CAP - 1));
-                    e = *slot;
-                    *slot = kSqEmpty;
-                }
-                left_before += left;
-            }
-            if (64 * wave < left_before) {
-                DDRR_PROF(PROF_POP);
-                DDRR_PROF_COUNT(PROF_N_BATCH, 1);
-                fwd_item<AUX, C>(p, lds_base, SG, range, e != kSqEmpty, e >> p.pix_bits, e & pix_mask,
-                                 out, aux, prof);
-            }
-        }
-    }
-#if defined(DDRR_BRICK_PROFILE)
-    DDRR_PROF(PROF_BARRIER);
-    if (lane == 0 && p.prof)
-        for (int i = 0; i < 16; ++i) atomicAdd(p.prof + i, prof.t[i]);
-#endif
-    // (a spin that ran into its bound: poison the result instead of returning a wrong image)
-    if (tid == 0 && *fault) (AUX ? aux : out)[0] = NAN;
-}
-
 // (vmin, vmax) of every brick of a BX x BY x BZ grid, the input of the 16-bit staging
 // (q16_range), and whether the brick can be quantised at all (brick_step.h q16_usable): its
 // LEVEL is the smallest mean |V| of any of its 4 x 4 x 4 blocks -- over the non-zero voxels when
@@ -1451,25 +1171,14 @@ __global__ __launch_bounds__(256) void brick_clear_kernel(float *__restrict__ bu
 }
 
 template <bool AUX, class C, bool PRE = false, bool SUB = false>
-int launch_cfg(const BrickArgs &p, int n_cu, float *out, float *aux, hipStream_t st) {
+int launch_cfg(const BrickArgs &p, int dev, int n_cu, float *out, float *aux, hipStream_t st) {
     static_assert(C::LDS <= C::LDS_BUDGET, "LDS budget");
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_set[kMaxDev] = {false};
+    static OncePerDevice lds_limit;
+    if (int rc = once_per_device(lds_limit, dev, [] {
+            return raise_lds_limit(&siddon_fwd_brick_kernel<AUX, C, PRE, SUB>, C::LDS);
+        }))
+        return rc;
     hipError_t e;
-    int dev = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return fail_hip(e, "hipGetDevice");
-    if (dev < 0 || dev >= kMaxDev) return fail(-1, "device index out of range");
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            if ((e = hipFuncSetAttribute(
-                     reinterpret_cast<const void *>(&siddon_fwd_brick_kernel<AUX, C, PRE, SUB>),
-                     hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS)) != hipSuccess)
-                return fail_hip(e, "hipFuncSetAttribute");
-            attr_set[dev] = true;
-        }
-    }
     const int nbx = (p.D.x + C::BX - 1) / C::BX, nby = (p.D.y + C::BY - 1) / C::BY;
     const int nbz = (p.D.z + C::BZ - 1) / C::BZ;
     const int n_bricks = nbx * nby * nbz, slots = n_cu * C::WGS_PER_CU;
@@ -1484,18 +1193,11 @@ int launch_cfg(const BrickArgs &p, int n_cu, float *out, float *aux, hipStream_t
             hipLaunchKernelGGL(brick_fingerprint_kernel, dim3((kFingerprintWords + 1023) / 1024), dim3(1024), 0, st,
                                p.vol, (long)p.D.x * p.D.y * p.D.z, const_cast<unsigned *>(p.fingerprint));
             if (p.packed) {
-                static bool pack_attr[kMaxDev] = {false};
-                {
-                    std::lock_guard<std::mutex> lock(mu);
-                    if (!pack_attr[dev]) {
-                        if ((e = hipFuncSetAttribute(
-                                 reinterpret_cast<const void *>(&brick_pack_kernel<C>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, C::BRICK_BYTES)) !=
-                            hipSuccess)
-                            return fail_hip(e, "hipFuncSetAttribute");
-                        pack_attr[dev] = true;
-                    }
-                }
+                static OncePerDevice pack_lds_limit;
+                if (int rc = once_per_device(pack_lds_limit, dev, [] {
+                        return raise_lds_limit(&brick_pack_kernel<C>, C::BRICK_BYTES);
+                    }))
+                    return rc;
                 hipLaunchKernelGGL(brick_pack_kernel<C>, dim3(n_bricks), dim3(C::THREADS),
                                    C::BRICK_BYTES, st, p, nby, nbz,
                                    const_cast<unsigned char *>(p.packed));
@@ -1524,48 +1226,6 @@ int launch_cfg(const BrickArgs &p, int n_cu, float *out, float *aux, hipStream_t
     }
     const dim3 grid(n_bricks < slots ? n_bricks : slots), block(C::THREADS);
     hipLaunchKernelGGL((siddon_fwd_brick_kernel<AUX, C, PRE, SUB>), grid, block, C::LDS, st, q, out, aux);
-    return 0;
-}
-
-template <bool AUX, class C, int NCLS>
-int launch_sq(const BrickArgs &p, int n_cu, float *out, float *aux, hipStream_t st) {
-    using S = SqCfg<NCLS, C>;
-    static_assert(S::LDS <= C::LDS_BUDGET, "LDS budget");
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_set[kMaxDev] = {false};
-    hipError_t e;
-    int dev = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return fail_hip(e, "hipGetDevice");
-    if (dev < 0 || dev >= kMaxDev) return fail(-1, "device index out of range");
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            if ((e = hipFuncSetAttribute(
-                     reinterpret_cast<const void *>(&siddon_fwd_brick_sq_kernel<AUX, C, NCLS>),
-                     hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS)) != hipSuccess)
-                return fail_hip(e, "hipFuncSetAttribute");
-            attr_set[dev] = true;
-        }
-    }
-    const int nbx = (p.D.x + C::BX - 1) / C::BX, nby = (p.D.y + C::BY - 1) / C::BY;
-    const int nbz = (p.D.z + C::BZ - 1) / C::BZ;
-    const int n_bricks = nbx * nby * nbz, slots = n_cu * C::WGS_PER_CU;
-    if (C::Q16) {
-        if (!p.ranges) return fail(-1, "DDRR_BRICKS_Q16 needs the brick_ranges workspace");
-        if (!p.ranges_valid)
-            hipLaunchKernelGGL(brick_range_kernel, dim3(n_bricks), dim3(256), 0, st, p.vol, p.D, C::BX,
-                               C::BY, C::BZ, nby, nbz, const_cast<float *>(p.ranges),
-                               const_cast<int *>(p.fallback), p.vec);
-        // (the shared-ring variants have no fp32 path: tools builds only)
-    }
-    const dim3 grid(n_bricks < slots ? n_bricks : slots), block(C::THREADS);
-    if (p.clear_n >= 0 && hipMemsetAsync(p.work, 0, 4 * sizeof(int), st) != hipSuccess)
-        return fail(-1, "hipMemsetAsync");
-    if (p.clear && p.clear_n > 0 &&
-        hipMemsetAsync(p.clear, 0, sizeof(float) * (size_t)p.clear_n, st) != hipSuccess)
-        return fail(-1, "hipMemsetAsync");
-    hipLaunchKernelGGL((siddon_fwd_brick_sq_kernel<AUX, C, NCLS>), grid, block, S::LDS, st, p, out, aux);
     return 0;
 }
 
@@ -1603,7 +1263,6 @@ bool order_bricks(BrickArgs &q, int BX, int BY, int BZ, int nby, int nbz, int n_
     return true;
 }
 
-// variant: DDRR_BRICKS_F32 (0) or DDRR_BRICKS_Q16 (1); tools builds know more (g_brick_variant)
 // bytes of the caller's brick workspace: the (min, max) pairs, 2 floats per 32^3 brick (any brick
 // grid fits), then, for the packed storage, the LDS images of the 32 x 32 x 64 bricks
 // layout: [header: 64 words, word 0 = bricks on the fp32 path, word 1 = bricks, word 2 = launches
@@ -1629,21 +1288,29 @@ long brick_workspace_bytes(int dx, int dy, int dz, int brick_storage) {
     return n;
 }
 
-int launch_fwd_bricks(int variant, int packed, float *brick_ranges, int ranges_valid,
-                      const float *volume, int dx, int dy, int dz, const float *source, const float *target,
-                      const float *img, int B, int det_h, int det_w, float voxel_shift, float eps,
-                      float *out, float *aux, float rec_q, hipStream_t st, void *launch_ws,
-                      const char *who, float *clear, long clear_n, const unsigned *pix_mask) {
-    const int N = det_h * det_w;
+// One configuration's instantiation for this launch: with the record or without, all pixels or those
+// of the mask.  PRE: the instantiation whose first claim hides the fingerprint's round trip.
+template <class C, bool PRE = false>
+static int launch_variant(const BrickLaunch &l, const BrickArgs &p, int dev, int n_cu) {
+    if (p.pix_mask)
+        return l.aux ? launch_cfg<true, C, PRE, true>(p, dev, n_cu, l.out, l.aux, l.st)
+                     : launch_cfg<false, C, PRE, true>(p, dev, n_cu, l.out, l.aux, l.st);
+    return l.aux ? launch_cfg<true, C, PRE, false>(p, dev, n_cu, l.out, l.aux, l.st)
+                 : launch_cfg<false, C, PRE, false>(p, dev, n_cu, l.out, l.aux, l.st);
+}
+
+// s.variant: DDRR_BRICKS_F32 (0) or DDRR_BRICKS_Q16 (1); tools builds know more (g_brick_variant)
+int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s) {
+    int variant = s.variant, ranges_valid = s.ranges_valid;
     // (brick_range_kernel: 16-byte loads where the volume's rows are aligned, else dwords)
-    const bool vec_ok = (dz & 3) == 0 && (reinterpret_cast<uintptr_t>(volume) & 15) == 0;
+    const bool vec_ok = (l.dz & 3) == 0 && (reinterpret_cast<uintptr_t>(l.volume) & 15) == 0;
     // the staging reads quads of four voxels from dword-aligned addresses (quad_load)
     // (brick_core.h quads_serve: at least four slices; thinner volumes take the general kernel)
-    const bool quads_ok = dz >= 4 && (long)dx * dy * dz >= 4 && (reinterpret_cast<uintptr_t>(volume) & 3) == 0;
+    const bool quads_ok = l.dz >= 4 && (long)l.dx * l.dy * l.dz >= 4 && (reinterpret_cast<uintptr_t>(l.volume) & 3) == 0;
     // fp32 bricks at a handful of poses: the general kernel (no pooled end, no hand-out order --
     // neither pays there): 7-12 % ahead at one pose, within 2 % from 8 on (profiles/r04/
     // fp32_bricks_general_vs_configurable.txt)
-    bool few_f32 = variant == DDRR_BRICKS_F32 && B < 8;
+    bool few_f32 = variant == DDRR_BRICKS_F32 && l.B < 8;
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
     if (g_brick_variant != -2) {  // (-2: no override, -1: bricks.hip)
         static int last_variant = -100;
@@ -1654,120 +1321,61 @@ int launch_fwd_bricks(int variant, int packed, float *brick_ranges, int ranges_v
     }
 #endif
     if (!quads_ok || variant < 0 || few_f32) {
-        if (clear && clear_n > 0 && hipMemsetAsync(clear, 0, sizeof(float) * (size_t)clear_n, st) != hipSuccess)
+        if (s.clear && s.clear_n > 0 &&
+            hipMemsetAsync(s.clear, 0, sizeof(float) * (size_t)s.clear_n, l.st) != hipSuccess)
             return fail(-1, "hipMemsetAsync");
-        return launch_bricks(aux ? BRICK_FWD_AUX : BRICK_FWD, volume, dx, dy, dz, source, target, img,
-                             nullptr, B, det_h, det_w, voxel_shift, eps, out, aux, nullptr, st,
-                             launch_ws, who, 0, nullptr, nullptr, rec_q, nullptr, 0, pix_mask);
+        return launch_bricks(l.aux ? BRICK_FWD_AUX : BRICK_FWD, l);
     }
-    BrickArgs p = {};
-    p.vol = volume;
-    p.D = Dims{dx, dy, dz};
-    p.source = source;
-    p.target = target;
-    p.img = img;
-    p.B = B;
-    p.det_h = det_h;
-    p.det_w = det_w;
-    p.shift = voxel_shift;
-    p.eps = eps;
+    BrickArgs p;
+    if (int rc = brick_args(l, p)) return rc;
     p.vec = vec_ok ? 1 : 0;
-    p.pix_mask = pix_mask;
-    if ((long)B * N * 12 >= (1L << 32))
-        return fail(-1, "B * N too large for one brick launch (12 B N must stay below 2^32): "
-                        "split the pose batch");
-    p.aux_plane = (unsigned)((long)B * N);
-    p.rec_q = rec_q;
-    p.ws_header = reinterpret_cast<int *>(brick_ranges);
-    p.ranges = brick_ranges ? brick_ranges + kWsHeaderBytes / sizeof(float) : nullptr;
-    p.fallback = brick_ranges ? reinterpret_cast<const int *>(p.ranges + 2 * n32_bricks(dx, dy, dz)) : nullptr;
+    float *const ws = s.brick_ranges;
+    p.ws_header = reinterpret_cast<int *>(ws);
+    p.ranges = ws ? ws + kWsHeaderBytes / sizeof(float) : nullptr;
+    p.fallback = ws ? reinterpret_cast<const int *>(p.ranges + 2 * n32_bricks(l.dx, l.dy, l.dz)) : nullptr;
     p.ranges_valid = ranges_valid;
-    p.packed = packed && brick_ranges
-                   ? reinterpret_cast<const unsigned char *>(brick_ranges) + ranges_bytes(dx, dy, dz)
-                   : nullptr;
-    p.fingerprint = brick_ranges ? reinterpret_cast<const unsigned *>(
-                                       reinterpret_cast<const unsigned char *>(brick_ranges) +
-                                       ranges_bytes(dx, dy, dz) - kFingerprintBytes)
-                                 : nullptr;
-    p.order = nullptr;
-    p.clear = clear;
-    p.clear_n = clear_n;
-    p.split_t = 0;
-    p.split_s = 1;
+    p.packed = s.packed && ws ? reinterpret_cast<const unsigned char *>(ws) + ranges_bytes(l.dx, l.dy, l.dz)
+                              : nullptr;
+    p.fingerprint = ws ? reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned char *>(ws) +
+                                                            ranges_bytes(l.dx, l.dy, l.dz) - kFingerprintBytes)
+                       : nullptr;
+    p.clear = s.clear;
+    p.clear_n = s.clear_n;
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
-    p.brick_times = g_brick_times;
+    // (experiments of this kernel alone: a given hand-out order, the last bricks split by poses)
     p.order = g_brick_order;
     p.split_t = g_brick_split_t;
     p.split_s = g_brick_split_s;
 #endif
-    p.pix_bits = 1;
-    while ((1L << p.pix_bits) < N) ++p.pix_bits;
-    if (((long)B << p.pix_bits) > (1L << 32))
-        return fail(-1, "B * 2^ceil(log2 N) exceeds 2^32: split the pose batch");
-    p.t1 = g_brick_t1;
-    p.t2 = g_brick_t2;
-    p.dbg = g_brick_dbg;
-#if defined(DDRR_BRICK_PROFILE)
-    p.prof = g_brick_prof;
-#endif
-#if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
-    if (variant >= 16) p.t1 = g_brick_sq_width;  // shared rings: t1 = class width
-#endif
-    int n_cu = 0;
-    if (int rc = brick_launch_resources(st, launch_ws, dx, dy, dz, n_cu, p.work, &p.order_ws, &p.order_cap,
-                                        /*zero_work=*/false))
-        return rc;
-#if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
-    if (g_brick_dbg & 512) p.order_ws = nullptr;  // (bricks in id order)
-#endif
-    int rc = 0;
-#define DDRR_LAUNCH_P(C, PRE_)                                                               \
-    (p.pix_mask ? (aux ? launch_cfg<true, C, PRE_, true>(p, n_cu, out, aux, st)             \
-                       : launch_cfg<false, C, PRE_, true>(p, n_cu, out, aux, st))           \
-                : (aux ? launch_cfg<true, C, PRE_, false>(p, n_cu, out, aux, st)            \
-                       : launch_cfg<false, C, PRE_, false>(p, n_cu, out, aux, st)))
-#define DDRR_LAUNCH(C) DDRR_LAUNCH_P(C, false)
     // (length-class thresholds: flat within 1.5 % around these, profiles/r03)
     if (variant == DDRR_BRICKS_Q16 || variant == 5) {
         p.t1 = g_brick_t1 * (22.f / 18.f);
         p.t2 = g_brick_t2 * (48.f / 40.f);
     }
+    int dev = 0, n_cu = 0;
+    if (int rc = brick_launch_resources(l, p, dev, n_cu, /*zero_work=*/false)) return rc;
+    int rc = 0;
     switch (variant) {
-        case DDRR_BRICKS_F32: rc = DDRR_LAUNCH(CfgF32); break;
-        case DDRR_BRICKS_Q16:
-            // (a few poses: the instantiation whose first claim hides the fingerprint's round trip)
-            if (B <= 8)
-                rc = DDRR_LAUNCH_P(CfgQ16Z64, true);
-            else
-                rc = DDRR_LAUNCH(CfgQ16Z64);
+        case DDRR_BRICKS_F32: rc = launch_variant<CfgF32>(l, p, dev, n_cu); break;
+        case DDRR_BRICKS_Q16:  // (PRE: a few poses)
+            rc = l.B <= 8 ? launch_variant<CfgQ16Z64, true>(l, p, dev, n_cu)
+                          : launch_variant<CfgQ16Z64>(l, p, dev, n_cu);
             break;
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
-        case 2: rc = DDRR_LAUNCH(CfgQ16x1); break;
-        case 10: rc = DDRR_LAUNCH(CfgQ16x2); break;
-        case 3: rc = DDRR_LAUNCH(CfgF32Half); break;
-        case 4: rc = DDRR_LAUNCH(CfgQ16X64); break;
-        case 5: rc = DDRR_LAUNCH(CfgQ16Z64); break;  // (= DDRR_BRICKS_Q16)
-        case 6: rc = DDRR_LAUNCH(CfgQ16Y64); break;
-        case 7: rc = DDRR_LAUNCH(CfgF32Y64); break;
-        case 8: rc = DDRR_LAUNCH(CfgF32X64); break;
-        case 9: rc = DDRR_LAUNCH(CfgF32Z64); break;
-        // workgroup-shared length-class rings: 16 + v: 12 classes, 32 + v: 8 classes
-#define DDRR_LAUNCH_SQ(C, K) (aux ? launch_sq<true, C, K>(p, n_cu, out, aux, st) \
-                                  : launch_sq<false, C, K>(p, n_cu, out, aux, st))
-        case 16: rc = DDRR_LAUNCH_SQ(CfgF32, 12); break;
-        case 18: rc = DDRR_LAUNCH_SQ(CfgQ16x1, 12); break;
-        case 20: rc = DDRR_LAUNCH_SQ(CfgQ16X64, 12); break;
-        case 21: rc = DDRR_LAUNCH_SQ(CfgQ16Z64, 12); break;
-        case 32: rc = DDRR_LAUNCH_SQ(CfgF32, 8); break;
-        case 36: rc = DDRR_LAUNCH_SQ(CfgQ16X64, 8); break;
-#undef DDRR_LAUNCH_SQ
+        case 2: rc = launch_variant<CfgQ16x1>(l, p, dev, n_cu); break;
+        case 10: rc = launch_variant<CfgQ16x2>(l, p, dev, n_cu); break;
+        case 3: rc = launch_variant<CfgF32Half>(l, p, dev, n_cu); break;
+        case 4: rc = launch_variant<CfgQ16X64>(l, p, dev, n_cu); break;
+        case 5: rc = launch_variant<CfgQ16Z64>(l, p, dev, n_cu); break;  // (= DDRR_BRICKS_Q16)
+        case 6: rc = launch_variant<CfgQ16Y64>(l, p, dev, n_cu); break;
+        case 7: rc = launch_variant<CfgF32Y64>(l, p, dev, n_cu); break;
+        case 8: rc = launch_variant<CfgF32X64>(l, p, dev, n_cu); break;
+        case 9: rc = launch_variant<CfgF32Z64>(l, p, dev, n_cu); break;
 #endif
         default: return fail(-1, "unknown brick variant");
     }
-#undef DDRR_LAUNCH
-#undef DDRR_LAUNCH_P
     if (rc) return rc;
-    return finish(who);
+    return finish(l.who);
 }
 
 }  // namespace ddrr_brick
@@ -1788,10 +1396,6 @@ extern "C" int ddrr_set_brick_order(const int *device_order) {
 extern "C" int ddrr_set_brick_split(int t, int s) {
     ddrr_brick::g_brick_split_t = t;
     ddrr_brick::g_brick_split_s = s < 1 ? 1 : s;
-    return 0;
-}
-extern "C" int ddrr_set_brick_sq_width(float w) {
-    ddrr_brick::g_brick_sq_width = w;
     return 0;
 }
 #endif

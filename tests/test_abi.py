@@ -153,8 +153,70 @@ def test_every_entry_rejects_null_pointers_and_negative_sizes_before_any_launch(
         # ... and through the binding: an exception that carries the entry's name and its message
         with pytest.raises(RuntimeError, match=name):
             lib.call(name, *[None if t is _lib._P else (0 if t in (_lib._I, _lib._L) else 0.0) for t in argtypes])
-    # argument rules of the image-space similarity entries, one by one
+    # argument rules of the brick entries (host pointers, an 8^3 volume: nothing is launched), as
+    # functions of (B, det_h, det_w, C, n_points); `alt`: the per-ray entry the channel cap points to
+    A = addr
+    channel_entries = {
+        "ddrr_siddon_forward_channels_bricks": ("ddrr_siddon_forward_channels", False, lambda B, h, w, C, n: (
+            A, A, 8, 8, 8, A, A, A, B, h, w, C, 0.5, 1e-8, A, A, None)),
+        "ddrr_siddon_forward_channels_bricks_words": ("ddrr_siddon_forward_channels", False, lambda B, h, w, C, n: (
+            A, 8, 8, 8, A, A, A, B, h, w, C, 0.5, 1e-8, A, A, None)),
+        "ddrr_siddon_backward_channels_bricks": ("ddrr_siddon_backward_channels", False, lambda B, h, w, C, n: (
+            A, A, 8, 8, 8, A, A, A, B, h, w, C, 0.5, 1e-8, A, A, None)),
+        "ddrr_trilinear_forward_channels_bricks": ("ddrr_trilinear_forward_channels", True, lambda B, h, w, C, n: (
+            A, A, 8, 8, 8, A, A, A, B, h, w, C, 0.5, 1e-8, n, A, A, A, A, None)),
+        "ddrr_trilinear_backward_channels_bricks": ("ddrr_trilinear_backward_channels", True, lambda B, h, w, C, n: (
+            A, A, 8, 8, 8, A, A, A, B, h, w, C, 0.5, 1e-8, n, A, A, A, A, None)),
+        "ddrr_siddon_backward_channels_volume_bricks": ("ddrr_siddon_backward_channels", False, lambda B, h, w, C, n: (
+            A, 8, 8, 8, A, A, A, A, B, h, w, C, 0.5, 1e-8, A, A, None)),
+        "ddrr_trilinear_backward_channels_volume_bricks": ("ddrr_trilinear_backward_channels", True,
+                                                           lambda B, h, w, C, n: (
+            A, 8, 8, 8, A, A, A, A, B, h, w, C, 0.5, 1e-8, n, A, A, A, A, None)),
+    }
+    brick_rows = []
+    for name, (alt, marcher, args) in channel_entries.items():
+        brick_rows += [(name, args(1, 1, 8, 2, 16), "2x2"), (name, args(1, 8, 1, 2, 16), "2x2"),
+                       (name, args(1, 8, 8, 0, 16), "C < 1"),
+                       (name, args(16384, 256, 256, 2, 16), f"use {alt}$"),
+                       # (N >= 2^22 is refused even for an empty batch)
+                       (name, args(0, 2048, 2048, 2, 16), f"use {alt}$")]
+        if marcher:
+            brick_rows.append((name, args(1, 8, 8, 2, 1), "n_points must be >= 2"))
+            no_amin = list(args(1, 8, 8, 2, 16))
+            no_amin[-5] = None
+            brick_rows.append((name, tuple(no_amin), "alphamin / alphamax or C < 1" if "volume" in name
+                               else "null alphamin / alphamax$"))
+        if "volume" not in name:  # (the volume gradients zero g_volume on the device)
+            brick_rows.append((name, args(0, 8, 8, 2, 16), None))
+
+    def fwd(B=1, h=8, w=8, out=A, vmax=0.0, storage=0, mask=False):
+        return (A, 8, 8, 8, A, A, A, B, h, w, 0.5, 1e-8, out, None, vmax, storage, None, 0, A) + \
+            ((mask,) if mask is not False else ()) + (None,)
+
+    def tri_fwd(B=1, h=8, w=8, n=16):
+        return (A, 8, 8, 8, A, A, A, B, h, w, 0.5, 1e-8, n, A, A, A, None, A, None)
+
+    def volgrad(tri, h=8, grad_out=A):
+        return (8, 8, 8, A, A, A, grad_out, 1, h, 8, 0.5, 1e-8) + ((16, A, A) if tri else ()) + (A, A, None)
+
+    brick_rows += [
+        ("ddrr_siddon_backward_volume_bricks", volgrad(False, h=1), "2x2"),
+        ("ddrr_siddon_backward_volume_bricks", volgrad(False, grad_out=None), "null grad_out / g_volume$"),
+        ("ddrr_trilinear_backward_volume_bricks", volgrad(True, h=1), "2x2"),
+        ("ddrr_trilinear_backward_volume_bricks", volgrad(True, grad_out=None),
+         "null grad_out / g_volume / alphamin / alphamax$"),
+        ("ddrr_trilinear_forward_bricks", tri_fwd(n=1), "n_points must be >= 2"),
+        ("ddrr_trilinear_forward_bricks", tri_fwd(h=1), "2x2"),
+        ("ddrr_trilinear_forward_bricks", tri_fwd(B=0), None),
+        ("ddrr_siddon_forward_bricks", fwd(storage=7), "brick_storage must be"),
+        ("ddrr_siddon_forward_bricks", fwd(vmax=-1.0), "record_vmax"),
+        ("ddrr_siddon_forward_bricks", fwd(B=0), None),
+        ("ddrr_siddon_forward_bricks_masked", fwd(mask=A + 1), "4-byte aligned"),
+        ("ddrr_siddon_forward_bricks_masked", fwd(mask=A, storage=7), "brick_storage must be"),
+        ("ddrr_siddon_forward_bricks_masked", fwd(B=0, mask=A), None)]
+    # ... and of the image-space similarity entries, one by one
     for name, args, what in (
+            *brick_rows,
             ("ddrr_blur_sobel_forward", (addr, 64, 1, 8, 8, addr, 4, addr, None), "odd number of taps"),
             ("ddrr_blur_sobel_forward", (addr, 64, 1, 8, 8, addr, 33, addr, None), "odd number of taps"),
             ("ddrr_blur_sobel_forward", (addr, 16, 1, 4, 4, addr, 9, addr, None), "reflect padding"),
@@ -164,6 +226,9 @@ def test_every_entry_rejects_null_pointers_and_negative_sizes_before_any_launch(
             ("ddrr_ncc_patch_forward", (addr, 5, addr, 1, 8, 8, 3, 1e-5, addr, None, None), "x1_stride"),
             ("ddrr_ncc_patch_backward", (addr, 64, addr, addr, addr, 2, 1, 8, 8, 3, addr, None), "g_stride"),
             ("ddrr_sobel_forward", (addr, 70000, 8, 8, addr, None), "65535")):
+        if what is None:  # a valid no-op: an empty batch
+            lib.call(name, *args)
+            continue
         with pytest.raises(RuntimeError, match=what):
             lib.call(name, *args)
 

@@ -730,6 +730,27 @@ def test_q16_bricks_small_ragged_sparse_and_many_poses(gpu, q16):
     nan = torch.isnan(dirty)
     assert nan[0, n_c] and not nan.all() and torch.equal(nan, torch.isnan(same))
     assert torch.allclose(dirty[~nan], clean[~nan], rtol=1e-5, atol=1e-5)  # (atomics: not bit-stable)
+    # a pixel mask (the subsampled forms of the kernels), on both sides of the pose counts at which the
+    # launcher changes kernel (fp32 bricks: B < 8, 16-bit bricks: B <= 8), with and without the record:
+    # 2 x 2 x 2 ragged 32 x 32 x 64 bricks, 2 x 2 x 3 ragged 32^3 ones; against the per-ray walk
+    H = W = 8
+    vol = torch.rand(33, 33, 65, generator=torch.Generator().manual_seed(3))
+    drr = DRR(make_subject(vol, spacing=(1.0, 1.0, 1.0)), sdd=300.0, height=H, width=W, delx=6.0).to(gpu)
+    keep = torch.tensor([0, 3, 9, 10, 27, 31, 32, 40, 63], device=gpu)
+    mask = ops.pixel_mask_of(keep, H * W)
+    for B in (1, 9):
+        g = torch.Generator().manual_seed(B)
+        rot = ((torch.rand(B, 3, generator=g) - 0.5) * 2.0).to(gpu)
+        xyz = (torch.tensor([0.0, 200.0, 0.0]) + (torch.rand(B, 3, generator=g) - 0.5) * 30).to(gpu)
+        s, t, L = voxel_rays(drr, rot, xyz)
+        ref, _, _ = ops.siddon_forward(drr.density, s, t, L, det=(H, W))
+        want = torch.zeros_like(ref)
+        want[:, keep] = ref[:, keep]
+        assert want.abs().max() > 0
+        for storage, aux in ((q16, False), (q16, True), ("f32", False), ("f32", True)):
+            got, _ = ops.siddon_forward_bricks(drr.density, s, t, L, (H, W), want_aux=aux, storage=storage,
+                                               pixel_mask=mask)
+            assert rel_err(got.cpu().numpy(), want.cpu().numpy()) < 2e-5, (B, storage, aux)
 
 
 @pytest.mark.parametrize("H,W", [(70, 45), (64, 64), (33, 130)])

@@ -23,13 +23,11 @@ ap.add_argument("--dbg", default="0")
 ap.add_argument("--classes", default="18:40")
 ap.add_argument("--order", default="id", help="hand-out order of the bricks: id | center | weight (comma list)")
 ap.add_argument("--split", default="0:1", help="T:S -- the last T bricks are handed out in S pose parts (comma list)")
-ap.add_argument("--sqw", default="8", help="class width(s) of the shared rings (variants >= 16)")
 ap.add_argument("--variants", default="-2",
                 help="bricks_fwd.hip variants: -2 product default, -1 the general 32^3 fp32 kernel of "
                      "bricks.hip, 0 32^3 fp32 (DDRR_BRICKS_F32), 1 = 5 32x32x64 16-bit (DDRR_BRICKS_Q16), "
                      "2 32^3 16-bit, 10 32^3 16-bit x 2 workgroups per CU, 3 32x32x16 fp32 x 2, 4 / 6 double "
-                     "16-bit bricks long in x / y, 7-9 anisotropic fp32 bricks 16x64x32, 64x16x32, 16x32x64; "
-                     "16 + v / 32 + v: workgroup-shared rings of 12 / 8 length classes")
+                     "16-bit bricks long in x / y, 7-9 anisotropic fp32 bricks 16x64x32, 64x16x32, 16x32x64")
 ap.add_argument("--storage", default="auto", help="auto (by variant) | f32 | q16 | q16p")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -88,16 +86,13 @@ def brick_order(kind, var, s_, t_):
 
 
 keep_alive = []
-for lay, dbg, cl, var, sqw, order, split in itertools.product(
-        a.layouts.split(","), a.dbg.split(","), a.classes.split(","), a.variants.split(","), a.sqw.split(","),
+for lay, dbg, cl, var, order, split in itertools.product(
+        a.layouts.split(","), a.dbg.split(","), a.classes.split(","), a.variants.split(","),
         a.order.split(","), a.split.split(",")):
     sy, sx = (int(v) for v in lay.split(":"))
     var = int(var)
-    if var < 16 and sqw != a.sqw.split(",")[0]:
-        continue
     lib.cdll.ddrr_set_brick_variant(var)
-    lib.cdll.ddrr_set_brick_sq_width(ctypes.c_float(float(sqw)))
-    storage = "q16" if var >= 0 and var % 16 in (1, 2, 4, 5, 6, 10) else "f32"
+    storage = "q16" if var in (1, 2, 4, 5, 6, 10) else "f32"
     if a.storage != "auto":
         storage = a.storage
     lib.cdll.ddrr_set_brick_debug(int(dbg))
@@ -106,7 +101,7 @@ for lay, dbg, cl, var, sqw, order, split in itertools.product(
     lib.cdll.ddrr_set_brick_classes(ctypes.c_float(t1), ctypes.c_float(t2))
     T_, S_ = (int(v) for v in split.split(":"))
     lib.cdll.ddrr_set_brick_split(T_, S_)
-    lay = f"dbg{dbg} cls{cl if var < 16 else sqw} var{var:2d} {storage} ord {order} split {split}"
+    lay = f"dbg{dbg} cls{cl} var{var:2d} {storage} ord {order} split {split}"
     rc = lib.cdll.ddrr_set_brick_layout(sy, sx)
     if rc != 0:
         print(f"layout {lay}: rejected")
