@@ -592,8 +592,8 @@ int ddrr_ncc_backward(const float *x1, long x1_stride, const float *x2, const fl
  * 256^2 at p = 13: 40 MB per image and pose) and autograd a dozen more; here a window is two passes over its
  * pixels in LDS.  x2 (B, H, W); x1 (B, H, W) with x1_stride = H W, or ONE image with x1_stride = 0.
  * out (B) (zeroed by the call).  coef (B, H-p+1, W-p+1, 4), 16-byte aligned, or NULL: per window
- * {1 / (s1 s2), mu1 / (s1 s2), ncc / s2^2, mu2 ncc / s2^2} for the backward, which forms
- * d out / d x2 (B, H, W) per pixel from the <= p^2 windows that hold it (g_out, g_stride: as
+ * {1 / (s1 s2), mu1, ncc / s2^2, mu2} for the backward, which forms d out / d x2 (B, H, W) per pixel
+ * from the <= p^2 windows that hold it, every term centred on its window's means (g_out, g_stride: as
  * ddrr_ncc_backward).  1 <= p <= min(H, W, 64). */
 int ddrr_ncc_patch_forward(const float *x1, long x1_stride, const float *x2, int B, int H, int W, int p,
                            float eps, float *out, float *coef, void *stream);
