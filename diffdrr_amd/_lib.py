@@ -28,6 +28,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_hip.so")
 ABI_VERSION = 33
 MI_ABI_VERSION = 1
 RECON_ABI_VERSION = 1
+FBP_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -232,3 +233,34 @@ def get_recon_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _recon_lib = recon_library(RECON_LIB_PATH)
     return _recon_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_fbp_hip.so
+# FDK initialisation: projection filter and voxel-driven backprojection (C ABI: include/diffdrr_fbp_hip.h)
+FBP_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_fbp_hip.so")
+FBP_HEADER = Header.read("diffdrr_fbp_hip.h", "ddrr_fbp", FBP_ABI_VERSION)
+_FBP_SIGNATURES, _FBP_RESTYPES, FBP_EXPORTS = FBP_HEADER.tables()
+FBP_MAX_IMAGE_DIM, FBP_MAX_VIEWS, FBP_MAX_DIM, FBP_VIEW_FLOATS = FBP_HEADER.constants(
+    "MAX_IMAGE_DIM", "MAX_VIEWS", "MAX_DIM", "VIEW_FLOATS")
+
+
+def fbp_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_fbp_hip.h."""
+    return DdrrLibrary(path, FBP_HEADER)
+
+
+_fbp_lib: DdrrLibrary | None = None
+
+
+def get_fbp_lib() -> DdrrLibrary:
+    """The FDK library, loaded on first use.  Raises if it has not been built."""
+    global _fbp_lib
+    if _fbp_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(FBP_LIB_PATH):
+            raise RuntimeError(
+                f"{FBP_LIB_PATH} is missing: the FDK kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _fbp_lib = fbp_library(FBP_LIB_PATH)
+    return _fbp_lib

@@ -1585,3 +1585,78 @@ def volume_adam_step(param, grad, exp_avg, exp_avg_sq, step, *, lr, betas=(0.9, 
         _launch_on(_lib.get_recon_lib(), "ddrr_recon_adam_step", param.device, (
             param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step.data_ptr(),
             param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), lo, hi, int(bool(maximize))))
+
+
+# ------------------------------------------------------------------ FDK initialisation (libdiffdrr_fbp_hip.so)
+def _check_projections(name, images):
+    if not torch.is_tensor(images) or images.dim() != 3:
+        raise ValueError(f"{name}: (B, H, W) images expected")
+    _check_volume_like(f"{name}: images", images)
+    _require_gpu(images)
+    if max(images.shape[1:]) > _lib.FBP_MAX_IMAGE_DIM:
+        raise ValueError(f"{name}: images of at most {_lib.FBP_MAX_IMAGE_DIM} pixels a side, got {tuple(images.shape)}")
+
+
+def fbp_filter(images, axis, taps, scale=1.0, *, u0=0.0, du=1.0, v0=0.0, dv=1.0, sdd=1.0, cosine_weight=False,
+               out=None):
+    """Cosine weighting and 1-D convolution of `images` (B, H, W) fp32 on the device in one pass
+    (include/diffdrr_fbp_hip.h ddrr_fbp_filter): along the columns within a row (`axis` 0) or along the
+    rows within a column (`axis` 1), `taps` (2 L - 1,) with lag 0 at index L - 1, L the filtered axis'
+    length.  -> `out` (a new tensor unless given; never `images` itself)."""
+    _check_projections("fbp_filter", images)
+    if axis not in (0, 1):
+        raise ValueError(f"fbp_filter: axis must be 0 (along columns) or 1 (along rows), not {axis!r}")
+    B, H, W = (int(d) for d in images.shape)
+    if images.numel() > 2**31:
+        raise ValueError(f"fbp_filter: at most 2^31 pixels, got {tuple(images.shape)}")
+    L = W if axis == 0 else H
+    _check_volume_like("fbp_filter: taps", taps)
+    if taps.device != images.device or tuple(taps.shape) != (max(2 * L - 1, 0),):
+        raise ValueError(f"fbp_filter: taps of shape ({2 * L - 1},) on {images.device} expected, got "
+                         f"{tuple(taps.shape)} on {taps.device}")
+    if cosine_weight and not float(sdd) > 0.0:
+        raise ValueError(f"fbp_filter: sdd must be > 0, not {sdd}")
+    if out is None:
+        out = torch.empty_like(images)
+    else:
+        _check_volume_like("fbp_filter: out", out, images)
+    if images.numel():
+        _launch_on(_lib.get_fbp_lib(), "ddrr_fbp_filter", images.device, (
+            images.data_ptr(), B, H, W, int(axis), taps.data_ptr(), float(scale), float(u0), float(du), float(v0),
+            float(dv), float(sdd), int(bool(cosine_weight)), out.data_ptr()))
+    return out
+
+
+def fbp_backproject(images, views, volume_shape=None, *, distance_weight=False, out=None, accumulate=False):
+    """Voxel-driven backprojection of `images` (B, H, W) fp32 on the device into a (Dx, Dy, Dz) volume
+    (include/diffdrr_fbp_hip.h ddrr_fbp_backproject): `views` (B, 16) holds per view the row-major 3 x 4
+    matrix voxel index -> (col U, row U, U) and a weight.  `out`: the volume to write (or, with
+    `accumulate`, to add to); a new one of `volume_shape` otherwise.  -> the volume."""
+    _check_projections("fbp_backproject", images)
+    B, H, W = (int(d) for d in images.shape)
+    _check_volume_like("fbp_backproject: views", views)
+    if views.device != images.device or tuple(views.shape) != (B, _lib.FBP_VIEW_FLOATS):
+        raise ValueError(f"fbp_backproject: views of shape ({B}, {_lib.FBP_VIEW_FLOATS}) on {images.device} expected, "
+                         f"got {tuple(views.shape)} on {views.device}")
+    if B > _lib.FBP_MAX_VIEWS:
+        raise ValueError(f"fbp_backproject: at most {_lib.FBP_MAX_VIEWS} views, got {B}")
+    if out is None:
+        if accumulate:
+            raise ValueError("fbp_backproject: accumulate needs an out tensor")
+        if volume_shape is None or len(volume_shape) != 3:
+            raise ValueError("fbp_backproject: a (Dx, Dy, Dz) volume_shape or an out tensor expected")
+        out = torch.empty(tuple(int(d) for d in volume_shape), dtype=torch.float32, device=images.device)
+    else:
+        _check_volume_like("fbp_backproject: out", out)
+        if out.dim() != 3 or out.device != images.device or (
+                volume_shape is not None and tuple(out.shape) != tuple(volume_shape)):
+            raise ValueError(f"fbp_backproject: out must be a (Dx, Dy, Dz) volume on {images.device}, got "
+                             f"{tuple(out.shape)} on {out.device}")
+    if max(out.shape) > _lib.FBP_MAX_DIM or out.numel() > 2**34:
+        raise ValueError(f"fbp_backproject: at most {_lib.FBP_MAX_DIM} voxels per axis and 2^34 in all, got "
+                         f"{tuple(out.shape)}")
+    if out.numel():
+        _launch_on(_lib.get_fbp_lib(), "ddrr_fbp_backproject", images.device, (
+            images.data_ptr(), B, H, W, views.data_ptr(), int(bool(distance_weight)), out.data_ptr(),
+            *(int(d) for d in out.shape), int(bool(accumulate))))
+    return out

@@ -218,6 +218,19 @@ class Reconstruction(nn.Module):
         self.density = nn.Parameter(init)
         self.lower, self.upper = lower, upper
 
+    @classmethod
+    def from_fdk(cls, drr, measured, *pose_args, window="ram-lak", lower: float | None = 0.0,
+                 upper: float | None = None, **kw):
+        """A ``Reconstruction`` that starts from the filtered backprojection of the views ``measured`` of a
+        full circular orbit (``analytic.fdk``: the pose arguments of ``DRR.forward``; ``view_weights=``,
+        ``isocenter=``), clamped to ``[lower, upper]``, instead of from zeros."""
+        from .analytic import fdk
+
+        start = fdk(drr, measured, *pose_args, window=window, **kw)
+        if lower is not None or upper is not None:
+            start = start.clamp(min=lower, max=upper)
+        return cls(drr, init=start.reshape(drr.density.shape), lower=lower, upper=upper)
+
     @contextmanager
     def _own_density(self):
         """``drr`` renders ``self.density`` for the length of the block: every route of ``DRR.forward``
