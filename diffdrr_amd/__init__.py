@@ -23,5 +23,5 @@ from .reconstruction import (  # noqa: F401
     VolumeAdam,
     total_variation_3d,
 )
-from .registration import GraphedIteration, PoseAdam, Registration  # noqa: F401
+from .registration import GraphedIteration, LevenbergMarquardt, PoseAdam, Registration  # noqa: F401
 from .renderers import Siddon, Trilinear  # noqa: F401

@@ -29,6 +29,7 @@ ABI_VERSION = 33
 MI_ABI_VERSION = 1
 RECON_ABI_VERSION = 1
 FBP_ABI_VERSION = 1
+LM_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -264,3 +265,34 @@ def get_fbp_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _fbp_lib = fbp_library(FBP_LIB_PATH)
     return _fbp_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_lm_hip.so
+# Levenberg-Marquardt registration: normal-equations sums and the step (C ABI: include/diffdrr_lm_hip.h)
+LM_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_lm_hip.so")
+LM_HEADER = Header.read("diffdrr_lm_hip.h", "ddrr_lm", LM_ABI_VERSION)
+_LM_SIGNATURES, _LM_RESTYPES, LM_EXPORTS = LM_HEADER.tables()
+LM_SUMS, LM_GROUP_RAYS, LM_STATE_DOUBLES, LM_MAX_POSES = LM_HEADER.constants(
+    "SUMS", "GROUP_RAYS", "STATE_DOUBLES", "MAX_POSES")
+
+
+def lm_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_lm_hip.h."""
+    return DdrrLibrary(path, LM_HEADER)
+
+
+_lm_lib: DdrrLibrary | None = None
+
+
+def get_lm_lib() -> DdrrLibrary:
+    """The Levenberg-Marquardt library, loaded on first use.  Raises if it has not been built."""
+    global _lm_lib
+    if _lm_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(LM_LIB_PATH):
+            raise RuntimeError(
+                f"{LM_LIB_PATH} is missing: the Levenberg-Marquardt kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _lm_lib = lm_library(LM_LIB_PATH)
+    return _lm_lib

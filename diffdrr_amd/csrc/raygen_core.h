@@ -121,10 +121,17 @@ DDRR_HD void pose_euler_forward(const float th[3], const float xyz[3], const int
     }
 }
 
-DDRR_HD void pose_euler_backward(const float th[3], const float xyz[3], const int axes[3],
-                                 const float *Ro, const float gMw[12], float g_th[3],
-                                 float g_xyz[3]) {
-    float E0[9], E1[9], E2[9], D0[9], D1[9], D2[9], T[9], R[9];
+// pose_euler_backward in two parts.  What depends on the pose alone -- R, v = to + xyz and the three
+// dR / dth_k, 39 floats -- is worked out once (pose_euler_adjoint_setup); the map gMw -> (g_th, g_xyz) on
+// them (pose_euler_adjoint_apply) is 72 fma and can be applied to many matrix gradients of one pose (the
+// Levenberg-Marquardt sums apply it per ray: lm_core.h).
+struct PoseEulerAdjoint {
+    float R[9], v[3], dR[27];  // dR[9 k + .] = dR / dth_k
+};
+
+DDRR_HD void pose_euler_adjoint_setup(const float th[3], const float xyz[3], const int axes[3],
+                                      const float *Ro, PoseEulerAdjoint &q) {
+    float E0[9], E1[9], E2[9], D0[9], D1[9], D2[9], T[9], A[9];
     elem_rot(axes[0], th[0], false, E0);
     elem_rot(axes[1], th[1], false, E1);
     elem_rot(axes[2], th[2], false, E2);
@@ -132,8 +139,18 @@ DDRR_HD void pose_euler_backward(const float th[3], const float xyz[3], const in
     elem_rot(axes[1], th[1], true, D1);
     elem_rot(axes[2], th[2], true, D2);
     mat3_mul(E0, E1, T);
-    mat3_mul(T, E2, R);
-    const float v[3] = {Ro[3] + xyz[0], Ro[7] + xyz[1], Ro[11] + xyz[2]};
+    mat3_mul(T, E2, q.R);
+    q.v[0] = Ro[3] + xyz[0], q.v[1] = Ro[7] + xyz[1], q.v[2] = Ro[11] + xyz[2];
+    mat3_mul(D0, E1, A);
+    mat3_mul(A, E2, q.dR);
+    mat3_mul(E0, D1, A);
+    mat3_mul(A, E2, q.dR + 9);
+    mat3_mul(T, D2, q.dR + 18);
+}
+
+// R (9), v (3), dR (27): the fields of a PoseEulerAdjoint, wherever they are kept
+DDRR_HD void pose_euler_adjoint_apply(const float *R, const float *v, const float *dR, const float *Ro,
+                                      const float gMw[12], float g_th[3], float g_xyz[3]) {
     // dL/dR = gMw[:, :3] Ro3^T + gMw[:, 3] (x) (to + xyz);  dL/dxyz = R^T gMw[:, 3]
     float GR[9];
 #pragma unroll
@@ -147,21 +164,21 @@ DDRR_HD void pose_euler_backward(const float th[3], const float xyz[3], const in
     for (int j = 0; j < 3; ++j)
         g_xyz[j] = fmaf(R[6 + j], gMw[11], fmaf(R[3 + j], gMw[7], R[j] * gMw[3]));
     // dL/dth_k = <dL/dR, dR/dth_k>
-    float A[9], Bm[9];
-    auto dot9 = [&](const float X[9]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
         float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) acc = fmaf(GR[k], X[k], acc);
-        return acc;
-    };
-    mat3_mul(D0, E1, A);
-    mat3_mul(A, E2, Bm);
-    g_th[0] = dot9(Bm);
-    mat3_mul(E0, D1, A);
-    mat3_mul(A, E2, Bm);
-    g_th[1] = dot9(Bm);
-    mat3_mul(T, D2, Bm);
-    g_th[2] = dot9(Bm);
+        for (int e = 0; e < 9; ++e) acc = fmaf(GR[e], dR[9 * k + e], acc);
+        g_th[k] = acc;
+    }
+}
+
+DDRR_HD void pose_euler_backward(const float th[3], const float xyz[3], const int axes[3],
+                                 const float *Ro, const float gMw[12], float g_th[3],
+                                 float g_xyz[3]) {
+    PoseEulerAdjoint q;
+    pose_euler_adjoint_setup(th, xyz, axes, Ro, q);
+    pose_euler_adjoint_apply(q.R, q.v, q.dR, Ro, gMw, g_th, g_xyz);
 }
 
 }  // namespace ddrr

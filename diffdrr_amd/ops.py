@@ -1660,3 +1660,84 @@ def fbp_backproject(images, views, volume_shape=None, *, distance_weight=False, 
             images.data_ptr(), B, H, W, views.data_ptr(), int(bool(distance_weight)), out.data_ptr(),
             *(int(d) for d in out.shape), int(bool(accumulate))))
     return out
+
+
+# ------------------------------------------------- Levenberg-Marquardt registration (libdiffdrr_lm_hip.so)
+def _launch_lm(name, device, *args):
+    """:func:`_launch` through the Levenberg-Marquardt library."""
+    _launch_on(_lib.get_lm_lib(), name, device, args)
+
+
+def _query_lm(name, *args):
+    return _lib.get_lm_lib().query(name, *args)
+
+
+def lm_workspace(B, N, device):
+    """The (uninitialised) per-workgroup partial sums of :func:`lm_normal_sums` for B poses of N rays:
+    (B, ceil(N / 1024), 44) float64."""
+    n = int(_query_lm("ddrr_lm_workspace_bytes", int(B), int(N))) // 8
+    return torch.empty(n, dtype=torch.float64, device=device).view(B, -1, _lib.LM_SUMS) if n else \
+        torch.empty(B, 0, _lib.LM_SUMS, dtype=torch.float64, device=device)
+
+
+def lm_state(B, damping, device):
+    """A fresh per-pose state of :func:`lm_step` (include/diffdrr_lm_hip.h): (B, 40) float64, zero but
+    for the damping."""
+    state = torch.zeros(B, _lib.LM_STATE_DOUBLES, dtype=torch.float64, device=device)
+    state[:, 34] = float(damping)
+    return state
+
+
+def lm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient34, *, eps=1e-8, with_img_path=True,
+                   ws=None, want_jacobian=False):
+    """The 44 normal-equations sums of every rendered pose from the brick kernel's blocked record ``aux``
+    (include/diffdrr_lm_hip.h ddrr_lm_normal_sums; ``fixed`` ((B | 1), N); the rest as
+    :func:`pose_raygen_forward` made them) -> (ws (B, G, 44) float64 per-workgroup partials,
+    jac (B, N, 6) float32 | None)."""
+    _require_gpu(rot)
+    B, N = rot.shape[0], P.shape[0]
+    if fixed.dim() != 2 or fixed.shape[0] not in (1, B) or fixed.shape[1] != N or fixed.dtype != torch.float32:
+        raise ValueError(f"lm_normal_sums: a float32 fixed image of shape (1 | {B}, {N}) expected, got "
+                         f"{tuple(fixed.shape)} {fixed.dtype}")
+    if B > _lib.LM_MAX_POSES:
+        raise ValueError(f"lm_normal_sums: at most {_lib.LM_MAX_POSES} poses, got {B}")
+    shared = fixed.shape[0] == 1 and B != 1
+    fixed, source, Mw, Ainv, P, rot, xyz, reorient34 = (
+        t.contiguous() for t in (fixed, source, Mw, Ainv, P, rot, xyz, reorient34))
+    dev = rot.device
+    if ws is None:
+        ws = lm_workspace(B, N, dev)
+    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != lm_workspace(B, N, "meta").numel():
+        raise ValueError("lm_normal_sums: ws must be what lm_workspace(B, N, device) returns")
+    jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
+    if B and N:
+        _launch_lm("ddrr_lm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), 0 if shared else N,
+                   source.data_ptr(), Mw.data_ptr(), Ainv.data_ptr(), P.data_ptr(), rot.data_ptr(), xyz.data_ptr(),
+                   *axes, reorient34.data_ptr(), B, N, float(eps), int(bool(with_img_path)), ws.data_ptr(),
+                   _ptr(jac))
+    return ws, jac
+
+
+def lm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, damping_min=1e-7, damping_max=1e6,
+            out=None):
+    """Accept or reject the rendered poses against ``state``, solve the damped normal equations of the best
+    ones and write the next trial poses into ``rot``, ``xyz`` IN PLACE (include/diffdrr_lm_hip.h
+    ddrr_lm_step) -> the best NCC per pose (B,) float32."""
+    _require_gpu(rot)
+    B = rot.shape[0]
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, 3):
+            raise ValueError("lm_step: contiguous float32 (B, 3) pose parameters")
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (B, _lib.LM_STATE_DOUBLES):
+        raise ValueError(f"lm_step: state must be a contiguous float64 (B, {_lib.LM_STATE_DOUBLES}) tensor")
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != lm_workspace(B, N, "meta").numel():
+        raise ValueError("lm_step: ws must be what lm_workspace(B, N, device) returns")
+    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
+        raise ValueError("lm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=rot.device)
+    if B:
+        _launch_lm("ddrr_lm_step", rot.device, ws.data_ptr(), state.data_ptr(), rot.data_ptr(), xyz.data_ptr(), B,
+                   int(N), float(ncc_eps), float(up), float(down), float(damping_min), float(damping_max),
+                   out.data_ptr())
+    return out

@@ -236,3 +236,195 @@ class GraphedIteration:
         self.graph.replay()
         self.iterations_done += 1
         return self.loss
+
+
+def normal_equations_reference(J: torch.Tensor, x: torch.Tensor, f: torch.Tensor, eps: float = 1e-5):
+    """The definition of what a Levenberg-Marquardt step solves, in float64 torch: with the residual
+    ``r = z(x) - z(f)``, ``z(v) = (v - mean v) / sqrt(var v + eps)`` (biased variance, as
+    ``NormalizedCrossCorrelation2d``) and ``J = dx / dtheta`` ((..., N, 6); ``x``, ``f`` (..., N))
+    -> ``(ncc, A, g)`` = (mean z(x) z(f), J_r^T J_r with the exact J_r = dz(x) / dtheta, J_r^T r), shapes
+    (...), (..., 6, 6), (..., 6).  ``1/2 |r|^2 = N (1 - ncc)`` up to ``eps``.  ``ddrr_lm_step`` forms the
+    same three from 44 sums (include/diffdrr_lm_hip.h); this function is the yardstick of its tests."""
+    J, x, f = J.double(), x.double(), f.double()
+    N = x.shape[-1]
+    mx, mf = x.mean(-1, keepdim=True), f.mean(-1, keepdim=True)
+    vx, vf = ((x - mx) ** 2).mean(-1, keepdim=True), ((f - mf) ** 2).mean(-1, keepdim=True)
+    sx, sf = (vx + eps).sqrt(), (vf + eps).sqrt()
+    zx, zf = (x - mx) / sx, (f - mf) / sf
+    # dz_n / dtheta = (J_n - mean J) / s_x - z_n (z^T J) / (N s_x)
+    Jc = J - J.mean(-2, keepdim=True)
+    zJ = (zx.unsqueeze(-1) * J).sum(-2, keepdim=True)
+    Jr = Jc / sx.unsqueeze(-1) - zx.unsqueeze(-1) * zJ / (N * sx.unsqueeze(-1))
+    r = zx - zf
+    return (zx * zf).mean(-1), Jr.transpose(-1, -2) @ Jr, (Jr * r.unsqueeze(-1)).sum(-2)
+
+
+class LevenbergMarquardt:
+    """Levenberg-Marquardt on the least-squares form of the global NCC, ``1/2 |z(drr) - z(fixed)|^2``,
+    for the Euler pose parameters of ``reg`` -- the second-order counterpart of the reference's
+    first-order loop (``notebooks/tutorials/registration.ipynb:240-316``): no learning rates, tens of
+    renders instead of hundreds.
+
+        lm = LevenbergMarquardt(reg, fixed)
+        for _ in range(30):
+            ncc = lm.step()        # (B,) best NCC so far per pose, a device tensor (no sync)
+        lm.commit()                # the best poses -> reg's parameters
+
+    ``step()`` is four launches and no host synchronisation: ``ddrr_pose_raygen_forward`` with the
+    clears, the brick kernel with its record and no image, ``ddrr_lm_normal_sums`` (the 6 x 6 normal
+    equations from the record, include/diffdrr_lm_hip.h) and ``ddrr_lm_step`` (accept / reject against the
+    best pose so far, damped solve, next trial).  Every render is a trial: BETWEEN steps ``reg``'s
+    parameters hold the next trial pose, not the best one -- ``commit()`` writes the best.  Several poses
+    are independent multi-starts, each with its own damping (``damping``, a read-only (B,) view).
+
+    Domain: that of ``DRR._render_euler_differentiable`` in radians -- Euler angles, a dense Siddon render
+    on the bricks of a volume that takes no gradient, float32 (B, 3) parameters on the volume's device, at
+    most ``DRR.FUSED_NCC_MAX_POSES`` poses; ``fixed`` ((1 | B), 1, H, W) float32.  Anything else raises
+    ``ValueError`` naming the condition.
+
+    ``graph=True`` (the step captured as one HIP graph, as ``GraphedIteration`` captures its iteration) is
+    not built: it raises ``NotImplementedError``.  Nothing in a step stands in its way -- no launch depends
+    on data, nothing is read back -- but the render's record is summed with float atomics, so a captured
+    step cannot be pinned bit for bit to the eager one, and it has not been run on a device."""
+
+    def __init__(self, reg: Registration, fixed: torch.Tensor, damping: float = 1.0, up: float = 4.0,
+                 down: float = 1.0 / 3.0, damping_min: float = 1e-7, damping_max: float = 1e6, eps: float = 1e-5,
+                 graph: bool = False):
+        from . import ops
+        from .pose import _AXIS, _check_convention
+        from .renderers import Siddon
+
+        if graph:
+            raise NotImplementedError("LevenbergMarquardt: graph=True (the step as one captured HIP graph) is not "
+                                      "built; run the eager step, which does not synchronise with the host either")
+        self.reg = reg
+        self.up, self.down, self.damping_min, self.damping_max, self.eps = (
+            float(up), float(down), float(damping_min), float(damping_max), float(eps))
+        if not (self.up > 1.0 and 0.0 < self.down < 1.0 and 0.0 < self.damping_min <= self.damping_max < float("inf")
+                and self.damping_min <= float(damping) <= self.damping_max and self.eps >= 0.0):
+            raise ValueError("LevenbergMarquardt: up > 1, 0 < down < 1, 0 < damping_min <= damping <= damping_max "
+                             "< inf and eps >= 0 expected")
+        drr = reg.drr
+        r, det = getattr(drr, "renderer", None), getattr(drr, "detector", None)
+        rot, xyz = reg._rotation, reg._translation
+
+        def refuse(what):
+            raise ValueError(f"LevenbergMarquardt: {what}")
+
+        if reg.parameterization != "euler_angles":
+            refuse(f"parameterization must be 'euler_angles', not {reg.parameterization!r}")
+        _check_convention(reg.convention)
+        if not isinstance(r, Siddon):
+            refuse("the renderer must be Siddon")
+        if r.grid_path != "bricks":
+            refuse("the Siddon renderer must take the brick kernel (grid_path == 'bricks')")
+        if r.packed_record:
+            refuse("the packed backward record (packed_record=True) is not read; use the float record")
+        if drr.density.requires_grad:
+            refuse("the volume must not require a gradient")
+        if drr.patch_size is not None:
+            refuse("patch_size must be None")
+        if det.n_subsample is not None:
+            refuse("p_subsample must be None (a dense detector)")
+        if not drr.fuse_ray_generation:
+            refuse("fuse_ray_generation must be on")
+        for name, t in (("rotation", rot), ("translation", xyz)):
+            if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32 or not t.is_contiguous():
+                refuse(f"{name} must be a contiguous float32 (B, 3) parameter, got {tuple(t.shape)} {t.dtype}")
+            if t.device != drr.density.device or not ops.on_device(t):
+                refuse(f"{name} must live on the volume's device ({drr.density.device}), got {t.device}")
+        B = rot.shape[0]
+        if rot.shape != xyz.shape:
+            refuse(f"rotation {tuple(rot.shape)} and translation {tuple(xyz.shape)} must have one shape")
+        if not 0 < B <= drr.FUSED_NCC_MAX_POSES:
+            refuse(f"1 ... {drr.FUSED_NCC_MAX_POSES} poses expected, got {B}")
+        H, W = det.height, det.width
+        if not (torch.is_tensor(fixed) and fixed.dim() == 4 and fixed.shape[0] in (1, B)
+                and tuple(fixed.shape[1:]) == (1, H, W) and fixed.dtype == torch.float32):
+            refuse(f"fixed must be a float32 ((1 | {B}), 1, {H}, {W}) tensor")
+        if fixed.device != rot.device:
+            refuse(f"fixed must live on the parameters' device ({rot.device}), got {fixed.device}")
+        self.B, self.N = B, H * W
+        self.axes = tuple(_AXIS[c] for c in reg.convention)
+        self.fixed = fixed.detach().reshape(fixed.shape[0], H * W).contiguous()
+        dev = rot.device
+        self._state = ops.lm_state(B, damping, dev)
+        self._ws = ops.lm_workspace(B, self.N, dev)
+        self._aux = ops.brick_record_buffer(B, self.N, dev)
+        self._ncc = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.steps_done = 0
+
+    # -- one render of the current parameters with its record: the first two launches of a step
+    def _render(self):
+        from . import ops
+        from .renderers import _brick_storage
+
+        drr, reg = self.reg.drr, self.reg
+        r, det = drr.renderer, drr.detector
+        P = drr._calibrated_points()
+        Ainv = drr._affine_inverse[0, :3, :] if drr._affine_inverse.dim() == 3 else drr._affine_inverse[:3, :]
+        cfg = r._cfg(False, det=(det.height, det.width))
+        reorient34 = det._reorient[:3, :].contiguous()
+        rot, xyz = reg._rotation.detach(), reg._translation.detach()
+        launch_ws = ops.launch_workspace(drr.density.shape, drr.density.device)
+        Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, self.axes, reorient34, Ainv, P, clear=self._aux,
+                                                          clear_launch_ws=launch_ws)
+        ops.siddon_forward_bricks(drr.density, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"],
+                                  eps=cfg["eps"], want_aux=True, storage=_brick_storage(drr.density, cfg, self.B),
+                                  want_image=False, aux=self._aux, launch_ws=launch_ws, cleared=True)
+        return dict(aux=self._aux, source=source, Mw=Mw, Ainv=Ainv, P=P, rot=rot, xyz=xyz, axes=self.axes,
+                    reorient34=reorient34), dict(eps=cfg["eps"], with_img_path=not cfg["stop_gradients"])
+
+    @torch.no_grad()
+    def _step(self, out):
+        from . import ops
+
+        args, kw = self._render()
+        ops.lm_normal_sums(args.pop("aux"), self.fixed, **args, **kw, ws=self._ws)
+        return ops.lm_step(self._ws, self._state, args["rot"], args["xyz"], self.N, ncc_eps=self.eps, up=self.up,
+                           down=self.down, damping_min=self.damping_min, damping_max=self.damping_max, out=out)
+
+    def step(self) -> torch.Tensor:
+        """Render the current parameters, accept or reject them, write the next trial into them
+        -> the best NCC per pose so far, (B,), detached."""
+        out = self._step(None)
+        self.steps_done += 1
+        return out
+
+    @torch.no_grad()
+    def commit(self):
+        """Copy the best pose of every start into ``reg``'s parameters (a start that has not rendered yet
+        keeps its parameters)."""
+        valid = self._state[:, 35:36] != 0
+        best = self._state[:, :6].to(torch.float32)
+        self.reg._rotation.copy_(torch.where(valid, best[:, :3], self.reg._rotation))
+        self.reg._translation.copy_(torch.where(valid, best[:, 3:], self.reg._translation))
+
+    @torch.no_grad()
+    def jacobian(self) -> torch.Tensor:
+        """d image / d (rot, xyz) at the current parameters, (B, N, 6) float32: one render and
+        ``ddrr_lm_normal_sums`` with its per-ray output.  The optimiser's state is not touched."""
+        from . import ops
+
+        args, kw = self._render()
+        return ops.lm_normal_sums(args.pop("aux"), self.fixed, **args, **kw, want_jacobian=True)[1]
+
+    @property
+    def damping(self) -> torch.Tensor:
+        view = self._state[:, 34].detach()
+        return view
+
+    @property
+    def best_parameters(self):
+        """(rotation, translation) of the best pose of every start so far, (B, 3) float32 each (copies)."""
+        best = self._state[:, :6].to(torch.float32)
+        return best[:, :3], best[:, 3:]
+
+    @property
+    def best_ncc(self) -> torch.Tensor:
+        return self._state[:, 6].detach()
+
+    @property
+    def accepted(self) -> torch.Tensor:
+        """(B,) bool: whether the last step's render became the best pose."""
+        return self._state[:, 36] != 0
