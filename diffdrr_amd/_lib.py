@@ -30,6 +30,7 @@ MI_ABI_VERSION = 1
 RECON_ABI_VERSION = 1
 FBP_ABI_VERSION = 1
 LM_ABI_VERSION = 1
+WARP_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -296,3 +297,34 @@ def get_lm_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _lm_lib = lm_library(LM_LIB_PATH)
     return _lm_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_warp_hip.so
+# Free-form deformation of the volume: the warp and its two adjoints (C ABI: include/diffdrr_warp_hip.h)
+WARP_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_warp_hip.so")
+WARP_HEADER = Header.read("diffdrr_warp_hip.h", "ddrr_warp", WARP_ABI_VERSION)
+_WARP_SIGNATURES, _WARP_RESTYPES, WARP_EXPORTS = WARP_HEADER.tables()
+WARP_PADDING_ZEROS, WARP_PADDING_BORDER, WARP_MAX_DIM, WARP_PIECE_VOXELS, WARP_PIECE_FLOATS = WARP_HEADER.constants(
+    "PADDING_ZEROS", "PADDING_BORDER", "MAX_DIM", "PIECE_VOXELS", "PIECE_FLOATS")
+
+
+def warp_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_warp_hip.h."""
+    return DdrrLibrary(path, WARP_HEADER)
+
+
+_warp_lib: DdrrLibrary | None = None
+
+
+def get_warp_lib() -> DdrrLibrary:
+    """The free-form deformation library, loaded on first use.  Raises if it has not been built."""
+    global _warp_lib
+    if _warp_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(WARP_LIB_PATH):
+            raise RuntimeError(
+                f"{WARP_LIB_PATH} is missing: the free-form deformation kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _warp_lib = warp_library(WARP_LIB_PATH)
+    return _warp_lib

@@ -1,0 +1,150 @@
+"""Free-form deformation of the volume in front of the renderers: ``W = V o (id + u)`` with ``u`` the
+trilinear interpolation of a control lattice, differentiable in the volume and in the lattice
+(``csrc/warp.hip``, ``include/diffdrr_warp_hip.h``: one fused forward kernel, an atomic-free lattice gradient,
+an atomic scatter for the volume gradient).  The torch composition it replaces -- ``F.interpolate`` of the
+lattice, a normalised grid, ``grid_sample`` -- materialises a (Dx, Dy, Dz, 3) grid and keeps it for backward.
+
+:func:`warp_reference` is the definition in pure torch, for any dtype: the float64 yardstick of the tests.
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import ops
+
+_PADDING = ("zeros", "border")
+
+
+# ------------------------------------------------------------------------------------------------ definition
+def _cells(D: int, G: int, device, dtype):
+    """Cell and fraction of every voxel of an axis (include/diffdrr_warp_hip.h): integers, then one division."""
+    num = torch.arange(D, device=device) * (G - 1)
+    c = torch.div(num, D - 1, rounding_mode="floor").clamp(max=G - 2)
+    return c, (num - c * (D - 1)).to(dtype) / (D - 1)
+
+
+def dense_field(displacement: torch.Tensor, shape) -> torch.Tensor:
+    """u (3, Dx, Dy, Dz): the lattice ``displacement`` (3, Gx, Gy, Gz) interpolated trilinearly at every voxel,
+    node i of axis a at voxel coordinate i (D_a - 1) / (G_a - 1)."""
+    u = displacement
+    for axis, D in enumerate(shape):
+        c, t = _cells(int(D), u.shape[axis + 1], u.device, u.dtype)
+        t = t.reshape([-1 if d == axis + 1 else 1 for d in range(4)])
+        u = (1 - t) * u.index_select(axis + 1, c) + t * u.index_select(axis + 1, c + 1)
+    return u
+
+
+def sample_coordinates(displacement: torch.Tensor, shape) -> torch.Tensor:
+    """p (3, Dx, Dy, Dz) = x + u(x), clamped to [-2, D_a + 1] (which changes no sample)."""
+    u = dense_field(displacement, shape)
+    p = []
+    for a, D in enumerate(shape):
+        x = torch.arange(int(D), device=u.device, dtype=u.dtype).reshape([-1 if d == a else 1 for d in range(3)])
+        p.append((x + u[a]).clamp(-2.0, float(D) + 1.0))
+    return torch.stack(p)
+
+
+def warp_reference(volume: torch.Tensor, displacement: torch.Tensor, padding: str = "zeros") -> torch.Tensor:
+    """The definition of :func:`warp_volume` by torch indexing, in the dtype of its arguments and on their
+    device; autograd gives both gradients (``floor`` has none: at f = 0 the derivative is the forward
+    difference)."""
+    if padding not in _PADDING:
+        raise ValueError(f"padding must be 'zeros' or 'border', not {padding!r}")
+    if volume.dim() != 3 or displacement.dim() != 4 or displacement.shape[0] != 3:
+        raise ValueError("a (Dx, Dy, Dz) volume and a (3, Gx, Gy, Gz) lattice expected")
+    if any(g < 2 or g > d for g, d in zip(displacement.shape[1:], volume.shape)):
+        raise ValueError("the lattice needs 2 <= G_a <= D_a nodes per axis")
+    p = sample_coordinates(displacement, volume.shape)
+    axes = []
+    for a, D in enumerate(volume.shape):
+        fl = p[a].detach().floor()
+        f = p[a] - fl
+        i = fl.long()
+        pair = []
+        for idx, w in ((i, 1 - f), (i + 1, f)):
+            if padding == "zeros":
+                w = w * ((idx >= 0) & (idx < D)).to(w.dtype)
+            pair.append((idx.clamp(0, D - 1), w))
+        axes.append(pair)
+    out = 0
+    for ix, wx in axes[0]:
+        for iy, wy in axes[1]:
+            for iz, wz in axes[2]:
+                out = out + wx * wy * wz * volume[ix, iy, iz]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+class _WarpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, volume, displacement, padding):
+        ctx.padding = padding
+        ctx.save_for_backward(volume, displacement)
+        return ops.warp_forward(volume, displacement, padding)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        volume, displacement = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        g_volume = ops.warp_backward_volume(displacement, grad_out, ctx.padding) if ctx.needs_input_grad[0] else None
+        g_disp = ops.warp_backward_displacement(volume, displacement, grad_out, ctx.padding) \
+            if ctx.needs_input_grad[1] else None
+        return g_volume, g_disp, None
+
+
+def warp_volume(volume: torch.Tensor, displacement: torch.Tensor, padding: str = "zeros") -> torch.Tensor:
+    """``W[x] = V(x + u(x))``: ``volume`` (Dx, Dy, Dz) and the lattice ``displacement`` (3, Gx, Gy, Gz), in
+    voxels of each axis, 2 <= G_a <= D_a, both float32, contiguous and on the GPU; trilinear sampling with
+    ``padding`` "zeros" or "border".  Differentiable in both arguments.  Anything outside that domain -- a CPU
+    tensor included: there is no CPU fallback -- raises ValueError naming the condition."""
+    ops._check_warp("warp_volume", getattr(volume, "shape", ()), displacement, padding, volume=volume)
+    return _WarpFn.apply(volume, displacement, padding)
+
+
+class FreeFormDeformation(nn.Module):
+    """A learnable smooth deformation of ``drr``'s volume in front of its renderer (between ``Registration``,
+    which moves six pose numbers, and ``Reconstruction``, which moves every voxel): ``displacement`` is an
+    ``nn.Parameter`` of zeros, (3, Gx, Gy, Gz), in MILLIMETRES along the volume's index axes; it is divided by
+    the voxel pitch (the column norms of ``drr``'s affine) and handed to :func:`warp_volume`.
+
+    ``forward`` renders the deformed volume through ``drr`` with the arguments and on the routes of a ``DRR``
+    whose own ``density`` requires a gradient; ``drr``'s own volume is read, never written."""
+
+    def __init__(self, drr, grid=(8, 8, 8), padding: str = "zeros"):
+        super().__init__()
+        if padding not in _PADDING:
+            raise ValueError(f"padding must be 'zeros' or 'border', not {padding!r}")
+        grid = tuple(int(g) for g in grid)
+        shape = tuple(drr.density.shape)
+        if len(grid) != 3 or any(g < 2 or g > d for g, d in zip(grid, shape)):
+            raise ValueError(f"grid must be (Gx, Gy, Gz) with 2 <= G_a <= D_a, got {grid} for a volume of {shape}")
+        if drr.density.dtype != torch.float32:
+            raise ValueError(f"a float32 volume expected, got {drr.density.dtype}")
+        self.drr = drr
+        self.padding = padding
+        dev = drr.density.device
+        affine = drr._affine.reshape(-1, 4, 4)[0, :3, :3]
+        self.register_buffer("pitch", affine.norm(dim=0).reshape(3, 1, 1, 1).to(dev, torch.float32).contiguous(),
+                             persistent=False)
+        self.displacement = nn.Parameter(torch.zeros(3, *grid, dtype=torch.float32, device=dev))
+
+    def warped(self) -> torch.Tensor:
+        """The deformed volume (the shape of ``drr``'s)."""
+        return warp_volume(self.drr.density, (self.displacement / self.pitch).contiguous(), self.padding)
+
+    def forward(self, *pose_args, **kwargs):
+        buffers = self.drr._buffers
+        theirs = buffers["density"]
+        buffers["density"] = self.warped()
+        try:
+            return self.drr(*pose_args, **kwargs)
+        finally:
+            buffers["density"] = theirs
+
+    def smoothness(self) -> torch.Tensor:
+        """Mean squared first difference of the lattice (mm^2), over the three lattice axes."""
+        d = self.displacement
+        diffs = [d.diff(dim=a + 1) for a in range(3)]
+        return sum(x.pow(2).sum() for x in diffs) / sum(x.numel() for x in diffs)

@@ -1741,3 +1741,87 @@ def lm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, dam
                    int(N), float(ncc_eps), float(up), float(down), float(damping_min), float(damping_max),
                    out.data_ptr())
     return out
+
+
+# ------------------------------------------------- free-form deformation (libdiffdrr_warp_hip.so)
+_WARP_PADDING = {"zeros": _lib.WARP_PADDING_ZEROS, "border": _lib.WARP_PADDING_BORDER}
+
+
+def _launch_warp(name, device, *args):
+    """:func:`_launch` through the free-form deformation library."""
+    _launch_on(_lib.get_warp_lib(), name, device, args)
+
+
+def _query_warp(name, *args):
+    return _lib.get_warp_lib().query(name, *args)
+
+
+def _check_warp(name, shape, displacement, padding, **volumes):
+    """The domain of include/diffdrr_warp_hip.h, each condition by name -> (dims, grid, padding code)."""
+    if padding not in _WARP_PADDING:
+        raise ValueError(f"{name}: padding must be 'zeros' or 'border', not {padding!r}")
+    for what, t in (("displacement", displacement), *volumes.items()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what}: a float32 tensor expected, got "
+                             f"{t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        if not on_device(t):
+            raise ValueError(f"{name}: {what} is on {t.device}: the warp kernels run on the GPU only (the package "
+                             "has no CPU fallback)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+        if t.device != displacement.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, the displacement on {displacement.device}")
+    dims = tuple(int(d) for d in shape)
+    if len(dims) != 3:
+        raise ValueError(f"{name}: a (Dx, Dy, Dz) volume expected, got shape {dims}")
+    for what, t in volumes.items():
+        if tuple(t.shape) != dims:
+            raise ValueError(f"{name}: {what} has shape {tuple(t.shape)}, expected {dims}")
+    if displacement.dim() != 4 or displacement.shape[0] != 3:
+        raise ValueError(f"{name}: a (3, Gx, Gy, Gz) displacement lattice expected, got shape "
+                         f"{tuple(displacement.shape)}")
+    grid = tuple(int(g) for g in displacement.shape[1:])
+    if max(dims) > _lib.WARP_MAX_DIM:
+        raise ValueError(f"{name}: at most {_lib.WARP_MAX_DIM} voxels per axis, got {dims}")
+    if dims[0] * dims[1] * dims[2] > 2**31:
+        raise ValueError(f"{name}: at most 2^31 voxels, got {dims} (larger volumes are out of scope)")
+    if any(g < 2 or g > d for g, d in zip(grid, dims)):
+        raise ValueError(f"{name}: the lattice needs 2 <= G_a <= D_a nodes per axis, got {grid} for a volume of {dims}")
+    return dims, grid, _WARP_PADDING[padding]
+
+
+def warp_forward(volume, displacement, padding="zeros"):
+    """W = V o (id + u), u the trilinear interpolation of the lattice ``displacement`` (3, Gx, Gy, Gz) in
+    voxels (include/diffdrr_warp_hip.h ddrr_warp_forward) -> W, a new tensor of the volume's shape."""
+    dims, grid, pad = _check_warp("warp_forward", getattr(volume, "shape", ()), displacement, padding, volume=volume)
+    out = torch.empty_like(volume)
+    _launch_warp("ddrr_warp_forward", volume.device, volume.data_ptr(), *dims, displacement.data_ptr(), *grid, pad,
+                 out.data_ptr())
+    return out
+
+
+def warp_backward_displacement(volume, displacement, grad_out, padding="zeros"):
+    """The lattice gradient of :func:`warp_forward` for the upstream ``grad_out`` (the volume's shape)
+    (ddrr_warp_backward_displacement: no atomics, bitwise reproducible) -> (3, Gx, Gy, Gz)."""
+    dims, grid, pad = _check_warp("warp_backward_displacement", getattr(volume, "shape", ()), displacement, padding,
+                                  volume=volume, grad_out=grad_out)
+    n = int(_query_warp("ddrr_warp_workspace_bytes", *dims, *grid))
+    if n < 0:
+        raise ValueError(f"warp_backward_displacement: a lattice of {grid} on a volume of {dims} needs more than "
+                         "2^31 - 1 (cell, piece) workgroups")
+    ws = torch.empty(n // 4, dtype=torch.float32, device=volume.device)
+    out = torch.empty_like(displacement)
+    _launch_warp("ddrr_warp_backward_displacement", volume.device, volume.data_ptr(), *dims, displacement.data_ptr(),
+                 *grid, pad, grad_out.data_ptr(), ws.data_ptr(), n, out.data_ptr())
+    return out
+
+
+def warp_backward_volume(displacement, grad_out, padding="zeros"):
+    """The volume gradient of :func:`warp_forward`: the trilinear scatter of ``grad_out`` (float atomics: not
+    bitwise reproducible on the device; ddrr_warp_backward_volume) -> the volume's shape."""
+    dims, grid, pad = _check_warp("warp_backward_volume", getattr(grad_out, "shape", ()), displacement, padding,
+                                  grad_out=grad_out)
+    out = torch.empty_like(grad_out)
+    _launch_warp("ddrr_warp_backward_volume", grad_out.device, displacement.data_ptr(), *grid, *dims, pad,
+                 grad_out.data_ptr(), out.data_ptr())
+    return out
