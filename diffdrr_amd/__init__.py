@@ -8,7 +8,7 @@ the reference's own module API (``DRR``, ``Detector``, ``RigidTransform`` /
 __version__ = "0.1.0"
 
 from .analytic import backproject, fbp_filter, fdk, ramp_taps  # noqa: F401
-from .deformation import FreeFormDeformation, warp_reference, warp_volume  # noqa: F401
+from .deformation import FreeFormDeformation, bspline_weights, dense_field, warp_reference, warp_volume  # noqa: F401
 from .detector import Detector  # noqa: F401
 from .drr import DRR  # noqa: F401
 from .metrics import (  # noqa: F401

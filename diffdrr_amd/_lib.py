@@ -31,6 +31,7 @@ RECON_ABI_VERSION = 1
 FBP_ABI_VERSION = 1
 LM_ABI_VERSION = 1
 WARP_ABI_VERSION = 1
+BSPLINE_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -328,3 +329,34 @@ def get_warp_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _warp_lib = warp_library(WARP_LIB_PATH)
     return _warp_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_bspline_hip.so
+# Cubic B-spline free-form deformation: the warp and its two adjoints (C ABI: include/diffdrr_bspline_hip.h)
+BSPLINE_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_bspline_hip.so")
+BSPLINE_HEADER = Header.read("diffdrr_bspline_hip.h", "ddrr_bspline", BSPLINE_ABI_VERSION)
+_BSPLINE_SIGNATURES, _BSPLINE_RESTYPES, BSPLINE_EXPORTS = BSPLINE_HEADER.tables()
+BSPLINE_PADDING_ZEROS, BSPLINE_PADDING_BORDER, BSPLINE_MAX_DIM, BSPLINE_CHUNK_VOXELS, BSPLINE_ROWS = \
+    BSPLINE_HEADER.constants("PADDING_ZEROS", "PADDING_BORDER", "MAX_DIM", "CHUNK_VOXELS", "ROWS")
+
+
+def bspline_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_bspline_hip.h."""
+    return DdrrLibrary(path, BSPLINE_HEADER)
+
+
+_bspline_lib: DdrrLibrary | None = None
+
+
+def get_bspline_lib() -> DdrrLibrary:
+    """The cubic B-spline deformation library, loaded on first use.  Raises if it has not been built."""
+    global _bspline_lib
+    if _bspline_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(BSPLINE_LIB_PATH):
+            raise RuntimeError(
+                f"{BSPLINE_LIB_PATH} is missing: the B-spline deformation kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _bspline_lib = bspline_library(BSPLINE_LIB_PATH)
+    return _bspline_lib

@@ -1825,3 +1825,60 @@ def warp_backward_volume(displacement, grad_out, padding="zeros"):
     _launch_warp("ddrr_warp_backward_volume", grad_out.device, displacement.data_ptr(), *grid, *dims, pad,
                  grad_out.data_ptr(), out.data_ptr())
     return out
+
+
+# ------------------------------------------------- cubic B-spline deformation (libdiffdrr_bspline_hip.so)
+_BSPLINE_PADDING = {"zeros": _lib.BSPLINE_PADDING_ZEROS, "border": _lib.BSPLINE_PADDING_BORDER}
+
+
+def _launch_bspline(name, device, *args):
+    """:func:`_launch` through the cubic B-spline deformation library."""
+    _launch_on(_lib.get_bspline_lib(), name, device, args)
+
+
+def _query_bspline(name, *args):
+    return _lib.get_bspline_lib().query(name, *args)
+
+
+def _check_bspline(name, shape, displacement, padding, **volumes):
+    """The domain of include/diffdrr_bspline_hip.h -- that of :func:`_check_warp`, each condition by name
+    -> (dims, grid, padding code)."""
+    dims, grid, _ = _check_warp(name, shape, displacement, padding, **volumes)
+    return dims, grid, _BSPLINE_PADDING[padding]
+
+
+def bspline_forward(volume, displacement, padding="zeros"):
+    """W = V o (id + u), u the cubic B-spline with the coefficients ``displacement`` (3, Gx, Gy, Gz) in voxels
+    (include/diffdrr_bspline_hip.h ddrr_bspline_forward; an approximating spline: u at a node is not the
+    node's coefficient) -> W, a new tensor of the volume's shape."""
+    dims, grid, pad = _check_bspline("bspline_forward", getattr(volume, "shape", ()), displacement, padding,
+                                     volume=volume)
+    out = torch.empty_like(volume)
+    _launch_bspline("ddrr_bspline_forward", volume.device, volume.data_ptr(), *dims, displacement.data_ptr(), *grid,
+                    pad, out.data_ptr())
+    return out
+
+
+def bspline_backward_displacement(volume, displacement, grad_out, padding="zeros"):
+    """The coefficient gradient of :func:`bspline_forward` for the upstream ``grad_out`` (the volume's shape)
+    (ddrr_bspline_backward_displacement: three gathers of fixed order, no atomics, bitwise reproducible)
+    -> (3, Gx, Gy, Gz)."""
+    dims, grid, pad = _check_bspline("bspline_backward_displacement", getattr(volume, "shape", ()), displacement,
+                                     padding, volume=volume, grad_out=grad_out)
+    n = int(_query_bspline("ddrr_bspline_workspace_bytes", *dims, *grid))
+    ws = torch.empty(n // 4, dtype=torch.float32, device=volume.device)
+    out = torch.empty_like(displacement)
+    _launch_bspline("ddrr_bspline_backward_displacement", volume.device, volume.data_ptr(), *dims,
+                    displacement.data_ptr(), *grid, pad, grad_out.data_ptr(), ws.data_ptr(), n, out.data_ptr())
+    return out
+
+
+def bspline_backward_volume(displacement, grad_out, padding="zeros"):
+    """The volume gradient of :func:`bspline_forward`: the trilinear scatter of ``grad_out`` (float atomics: not
+    bitwise reproducible on the device; ddrr_bspline_backward_volume) -> the volume's shape."""
+    dims, grid, pad = _check_bspline("bspline_backward_volume", getattr(grad_out, "shape", ()), displacement,
+                                     padding, grad_out=grad_out)
+    out = torch.empty_like(grad_out)
+    _launch_bspline("ddrr_bspline_backward_volume", grad_out.device, displacement.data_ptr(), *grid, *dims, pad,
+                    grad_out.data_ptr(), out.data_ptr())
+    return out
