@@ -17,6 +17,13 @@ from .metrics import (  # noqa: F401
     MutualInformation,
     NormalizedCrossCorrelation2d,
 )
+from .polyrigid import (  # noqa: F401
+    PolyRigidDeformation,
+    polyrigid_reference,
+    polyrigid_warp,
+    twist_lattice,
+    weights_from_labels,
+)
 from .pose import RigidTransform, convert  # noqa: F401
 from .reconstruction import (  # noqa: F401
     Reconstruction,

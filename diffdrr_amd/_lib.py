@@ -32,6 +32,7 @@ FBP_ABI_VERSION = 1
 LM_ABI_VERSION = 1
 WARP_ABI_VERSION = 1
 BSPLINE_ABI_VERSION = 1
+POLYRIGID_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -360,3 +361,39 @@ def get_bspline_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _bspline_lib = bspline_library(BSPLINE_LIB_PATH)
     return _bspline_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_polyrigid_hip.so
+# Polyrigid deformation of the volume: the warp and its two adjoints (C ABI: include/diffdrr_polyrigid_hip.h)
+POLYRIGID_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_polyrigid_hip.so")
+POLYRIGID_HEADER = Header.read("diffdrr_polyrigid_hip.h", "ddrr_polyrigid", POLYRIGID_ABI_VERSION)
+_POLYRIGID_SIGNATURES, _POLYRIGID_RESTYPES, POLYRIGID_EXPORTS = POLYRIGID_HEADER.tables()
+POLYRIGID_PADDING_ZEROS, POLYRIGID_PADDING_BORDER, POLYRIGID_MAX_DIM, POLYRIGID_PIECE_VOXELS, \
+    POLYRIGID_PIECE_FLOATS = POLYRIGID_HEADER.constants(
+        "PADDING_ZEROS", "PADDING_BORDER", "MAX_DIM", "PIECE_VOXELS", "PIECE_FLOATS")
+# A, B, C of the SE(3) exponential: Taylor series of POLYRIGID_SERIES_TERMS terms in s = |omega|^2 below the seam
+POLYRIGID_SERIES_TERMS, _num, _den = POLYRIGID_HEADER.constants(
+    "SERIES_TERMS", "SERIES_BELOW_NUM", "SERIES_BELOW_DEN")
+POLYRIGID_SERIES_BELOW = _num / _den
+
+
+def polyrigid_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_polyrigid_hip.h."""
+    return DdrrLibrary(path, POLYRIGID_HEADER)
+
+
+_polyrigid_lib: DdrrLibrary | None = None
+
+
+def get_polyrigid_lib() -> DdrrLibrary:
+    """The polyrigid deformation library, loaded on first use.  Raises if it has not been built."""
+    global _polyrigid_lib
+    if _polyrigid_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(POLYRIGID_LIB_PATH):
+            raise RuntimeError(
+                f"{POLYRIGID_LIB_PATH} is missing: the polyrigid deformation kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _polyrigid_lib = polyrigid_library(POLYRIGID_LIB_PATH)
+    return _polyrigid_lib

@@ -1882,3 +1882,92 @@ def bspline_backward_volume(displacement, grad_out, padding="zeros"):
     _launch_bspline("ddrr_bspline_backward_volume", grad_out.device, displacement.data_ptr(), *grid, *dims, pad,
                     grad_out.data_ptr(), out.data_ptr())
     return out
+
+
+# ------------------------------------------------- polyrigid deformation (libdiffdrr_polyrigid_hip.so)
+_POLYRIGID_PADDING = {"zeros": _lib.POLYRIGID_PADDING_ZEROS, "border": _lib.POLYRIGID_PADDING_BORDER}
+
+
+def _launch_polyrigid(name, device, *args):
+    """:func:`_launch` through the polyrigid deformation library."""
+    _launch_on(_lib.get_polyrigid_lib(), name, device, args)
+
+
+def _query_polyrigid(name, *args):
+    return _lib.get_polyrigid_lib().query(name, *args)
+
+
+def _check_polyrigid(name, shape, twists, pitch, padding, **volumes):
+    """The domain of include/diffdrr_polyrigid_hip.h, each condition by name
+    -> (dims, grid, pitch as three floats, padding code)."""
+    if padding not in _POLYRIGID_PADDING:
+        raise ValueError(f"{name}: padding must be 'zeros' or 'border', not {padding!r}")
+    for what, t in (("twists", twists), *volumes.items()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what}: a float32 tensor expected, got "
+                             f"{t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        if not on_device(t):
+            raise ValueError(f"{name}: {what} is on {t.device}: the polyrigid kernels run on the GPU only (the "
+                             "package has no CPU fallback)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+        if t.device != twists.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, the twists on {twists.device}")
+    dims = tuple(int(d) for d in shape)
+    if len(dims) != 3:
+        raise ValueError(f"{name}: a (Dx, Dy, Dz) volume expected, got shape {dims}")
+    for what, t in volumes.items():
+        if tuple(t.shape) != dims:
+            raise ValueError(f"{name}: {what} has shape {tuple(t.shape)}, expected {dims}")
+    if twists.dim() != 4 or twists.shape[0] != 6:
+        raise ValueError(f"{name}: a (6, Gx, Gy, Gz) twist lattice expected, got shape {tuple(twists.shape)}")
+    grid = tuple(int(g) for g in twists.shape[1:])
+    if max(dims) > _lib.POLYRIGID_MAX_DIM:
+        raise ValueError(f"{name}: at most {_lib.POLYRIGID_MAX_DIM} voxels per axis, got {dims}")
+    if dims[0] * dims[1] * dims[2] > 2**31:
+        raise ValueError(f"{name}: at most 2^31 voxels, got {dims} (larger volumes are out of scope)")
+    if any(g < 2 or g > d for g, d in zip(grid, dims)):
+        raise ValueError(f"{name}: the lattice needs 2 <= G_a <= D_a nodes per axis, got {grid} for a volume of {dims}")
+    pitch = tuple(float(h) for h in pitch)
+    if len(pitch) != 3 or not all(0.0 < h < float("inf") for h in pitch):
+        raise ValueError(f"{name}: the voxel pitch must be three positive finite numbers (mm), got {pitch}")
+    return dims, grid, pitch, _POLYRIGID_PADDING[padding]
+
+
+def polyrigid_forward(volume, twists, pitch=(1.0, 1.0, 1.0), padding="zeros"):
+    """W = V o (id + u), u(x) = (exp(xi(x)) y - y) / pitch with xi the trilinear interpolation of the twist lattice
+    ``twists`` (6, Gx, Gy, Gz) = (omega in radians, v in mm) and y the voxel's position in mm from the volume's
+    centre (include/diffdrr_polyrigid_hip.h ddrr_polyrigid_forward) -> W, a new tensor of the volume's shape."""
+    dims, grid, h, pad = _check_polyrigid("polyrigid_forward", getattr(volume, "shape", ()), twists, pitch, padding,
+                                          volume=volume)
+    out = torch.empty_like(volume)
+    _launch_polyrigid("ddrr_polyrigid_forward", volume.device, volume.data_ptr(), *dims, twists.data_ptr(), *grid, *h,
+                      pad, out.data_ptr())
+    return out
+
+
+def polyrigid_backward_twists(volume, twists, grad_out, pitch=(1.0, 1.0, 1.0), padding="zeros"):
+    """The twist-lattice gradient of :func:`polyrigid_forward` for the upstream ``grad_out`` (the volume's shape)
+    (ddrr_polyrigid_backward_twists: no atomics, bitwise reproducible) -> (6, Gx, Gy, Gz)."""
+    dims, grid, h, pad = _check_polyrigid("polyrigid_backward_twists", getattr(volume, "shape", ()), twists, pitch,
+                                          padding, volume=volume, grad_out=grad_out)
+    n = int(_query_polyrigid("ddrr_polyrigid_workspace_bytes", *dims, *grid))
+    if n < 0:
+        raise ValueError(f"polyrigid_backward_twists: a lattice of {grid} on a volume of {dims} needs more than "
+                         "2^31 - 1 (cell, piece) workgroups")
+    ws = torch.empty(n // 4, dtype=torch.float32, device=volume.device)
+    out = torch.empty_like(twists)
+    _launch_polyrigid("ddrr_polyrigid_backward_twists", volume.device, volume.data_ptr(), *dims, twists.data_ptr(),
+                      *grid, *h, pad, grad_out.data_ptr(), ws.data_ptr(), n, out.data_ptr())
+    return out
+
+
+def polyrigid_backward_volume(twists, grad_out, pitch=(1.0, 1.0, 1.0), padding="zeros"):
+    """The volume gradient of :func:`polyrigid_forward`: the trilinear scatter of ``grad_out`` (float atomics: not
+    bitwise reproducible on the device; ddrr_polyrigid_backward_volume) -> the volume's shape."""
+    dims, grid, h, pad = _check_polyrigid("polyrigid_backward_volume", getattr(grad_out, "shape", ()), twists, pitch,
+                                          padding, grad_out=grad_out)
+    out = torch.empty_like(grad_out)
+    _launch_polyrigid("ddrr_polyrigid_backward_volume", grad_out.device, twists.data_ptr(), *grid, *dims, *h, pad,
+                      grad_out.data_ptr(), out.data_ptr())
+    return out

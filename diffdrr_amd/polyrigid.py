@@ -1,0 +1,235 @@
+"""Polyrigid deformation of the volume in front of the renderers: ``K`` bodies, each with its own rigid motion
+(a twist ``theta_k = (omega_k, v_k)``: a rotation vector in radians, a translation in mm), and smooth spatial
+weights that say which body a point belongs to.  The motions are blended in the Lie algebra (the log-Euclidean
+polyrigid model of Arsigny et al.), so the result is one smooth warp, ``W(x) = V(x + u(x))`` with
+``u(x) = exp(sum_k w_k(x) theta_k) y - y``, exactly rigid wherever one weight is 1 -- what a free-form lattice has
+to be regularised into for anatomy that articulates but does not bend, in ``6 K`` parameters.
+
+``csrc/polyrigid.hip`` (``include/diffdrr_polyrigid_hip.h`` has the definitions) is one fused forward kernel, an
+atomic-free twist gradient and an atomic scatter for the volume gradient: no dense twist or displacement field
+exists in memory.  The weights live on a lattice (``K, Gx, Gy, Gz``) and interpolate trilinearly, so a body is
+exactly rigid only over the lattice cells where its weight is 1 at all eight nodes; a lattice as fine as the
+volume is allowed.
+
+:func:`polyrigid_reference` is the definition in pure torch, for any dtype: the float64 yardstick of the tests.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+from torch import nn
+
+from . import _lib, ops
+from .deformation import _PADDING, dense_field, sample_displaced
+
+SERIES_BELOW, SERIES_TERMS = _lib.POLYRIGID_SERIES_BELOW, _lib.POLYRIGID_SERIES_TERMS
+
+
+def twist_lattice(theta: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """Xi (6, Gx, Gy, Gz): ``Xi[c, n] = sum_k weights[k, n] theta[k, c]`` -- the bodies' twists ``theta`` (K, 6)
+    blended in the Lie algebra by the lattice ``weights`` (K, Gx, Gy, Gz)."""
+    if theta.dim() != 2 or theta.shape[1] != 6 or weights.dim() != 4 or weights.shape[0] != theta.shape[0]:
+        raise ValueError(f"twists of shape (K, 6) and weights of shape (K, Gx, Gy, Gz) expected, got "
+                         f"{tuple(theta.shape)} and {tuple(weights.shape)}")
+    return torch.einsum("kxyz,kc->cxyz", weights, theta).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ definition
+def _series(s, first):
+    """sum_n (-s)^n / (2n + first)!, SERIES_TERMS terms, by Horner's rule."""
+    v = torch.full_like(s, 1.0 / math.factorial(2 * (SERIES_TERMS - 1) + first))
+    for n in range(SERIES_TERMS - 2, -1, -1):
+        v = 1.0 / math.factorial(2 * n + first) - s * v
+    return v
+
+
+def exponential_coefficients(s: torch.Tensor):
+    """A = sin(phi) / phi, B = (1 - cos(phi)) / phi^2, C = (phi - sin(phi)) / phi^3 as functions of s = phi^2:
+    their Taylor series in s below SERIES_BELOW, the closed forms from there on (include/diffdrr_polyrigid_hip.h)."""
+    low = s < SERIES_BELOW
+    safe = torch.where(low, torch.full_like(s, SERIES_BELOW), s)  # (no 0 / 0 on the branch not taken)
+    phi = safe.sqrt()
+    sn, cs = phi.sin(), phi.cos()
+    return (torch.where(low, _series(s, 1), sn / phi), torch.where(low, _series(s, 2), (1 - cs) / safe),
+            torch.where(low, _series(s, 3), (phi - sn) / (safe * phi)))
+
+
+def _cross(a, b):
+    return torch.stack((a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]))
+
+
+def centred_coordinates(shape, pitch, device, dtype) -> torch.Tensor:
+    """y (3, Dx, Dy, Dz): every voxel's position in mm from the volume's centre, y_a = h_a (x_a - (D_a - 1) / 2)."""
+    axes = [float(h) * (torch.arange(int(D), device=device, dtype=dtype) - 0.5 * (int(D) - 1))
+            for D, h in zip(shape, pitch)]
+    return torch.stack(torch.meshgrid(*axes, indexing="ij"))
+
+
+def displacement_field(twists: torch.Tensor, shape, pitch=(1.0, 1.0, 1.0)) -> torch.Tensor:
+    """u (3, Dx, Dy, Dz) in voxels of each axis: the twist lattice (6, Gx, Gy, Gz) interpolated trilinearly to
+    every voxel, then ``exp(xi) y - y`` there, formed directly (include/diffdrr_polyrigid_hip.h)."""
+    xi = dense_field(twists, shape)
+    w, v = xi[:3], xi[3:]
+    y = centred_coordinates(shape, pitch, xi.device, xi.dtype)
+    A, B, C = exponential_coefficients((w * w).sum(0))
+    u_mm = _cross(w, A * y + B * v) + _cross(w, _cross(w, B * y + C * v)) + v
+    h = torch.tensor([float(p) for p in pitch], device=xi.device, dtype=xi.dtype).reshape(3, 1, 1, 1)
+    return u_mm / h
+
+
+def _check_definition(volume, twists, padding):
+    if padding not in _PADDING:
+        raise ValueError(f"padding must be 'zeros' or 'border', not {padding!r}")
+    if volume.dim() != 3 or twists.dim() != 4 or twists.shape[0] != 6:
+        raise ValueError("a (Dx, Dy, Dz) volume and a (6, Gx, Gy, Gz) twist lattice expected")
+    if any(g < 2 or g > d for g, d in zip(twists.shape[1:], volume.shape)):
+        raise ValueError("the lattice needs 2 <= G_a <= D_a nodes per axis")
+
+
+def polyrigid_reference(volume: torch.Tensor, theta: torch.Tensor, weights: torch.Tensor, pitch=(1.0, 1.0, 1.0),
+                        padding: str = "zeros") -> torch.Tensor:
+    """The definition of :func:`polyrigid_warp` by torch indexing, in the dtype of its arguments and on their
+    device; autograd gives every gradient (``floor`` has none: at f = 0 the derivative is the forward difference)."""
+    twists = twist_lattice(theta, weights)
+    _check_definition(volume, twists, padding)
+    return sample_displaced(volume, displacement_field(twists, volume.shape, pitch), padding)
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+class _PolyRigidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, volume, twists, pitch, padding):
+        ctx.pitch, ctx.padding = pitch, padding
+        ctx.save_for_backward(volume, twists)
+        return ops.polyrigid_forward(volume, twists, pitch, padding)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        volume, twists = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        g_volume = ops.polyrigid_backward_volume(twists, grad_out, ctx.pitch, ctx.padding) \
+            if ctx.needs_input_grad[0] else None
+        g_twists = ops.polyrigid_backward_twists(volume, twists, grad_out, ctx.pitch, ctx.padding) \
+            if ctx.needs_input_grad[1] else None
+        return g_volume, g_twists, None, None
+
+
+def polyrigid_warp(volume: torch.Tensor, theta: torch.Tensor, weights: torch.Tensor, pitch=(1.0, 1.0, 1.0),
+                   padding: str = "zeros") -> torch.Tensor:
+    """``W[x] = V(x + u(x))``, ``u(x) = (exp(xi(x)) y - y) / pitch``: ``volume`` (Dx, Dy, Dz), the bodies' twists
+    ``theta`` (K, 6) = (rotation vector in radians, translation in mm), their lattice ``weights`` (K, Gx, Gy, Gz)
+    (non-negative, summing to 1 over k at every node; 2 <= G_a <= D_a) and the voxel ``pitch`` in mm; all tensors
+    float32 and on the GPU; trilinear sampling with ``padding`` "zeros" or "border".  Differentiable in
+    ``volume``, ``theta`` and ``weights``.  Anything outside that domain -- a CPU tensor included: there is no CPU
+    fallback -- raises ValueError naming the condition."""
+    for what, t in (("theta", theta), ("weights", weights)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"polyrigid_warp: {what}: a float32 tensor expected, got "
+                             f"{t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    twists = twist_lattice(theta, weights)
+    _, _, pitch, _ = ops._check_polyrigid("polyrigid_warp", getattr(volume, "shape", ()), twists, pitch, padding,
+                                          volume=volume)
+    return _PolyRigidFn.apply(volume, twists, pitch, padding)
+
+
+class PolyRigidDeformation(nn.Module):
+    """A learnable articulated deformation of ``drr``'s volume in front of its renderer: ``K`` rigid bodies with
+    the parameters ``rotation`` (K, 3), rotation vectors in radians, and ``translation`` (K, 3) in MILLIMETRES
+    along the volume's index axes about its centre, both zero at the start, and the fixed buffer ``weights``
+    (K, Gx, Gy, Gz) -- validated (finite, non-negative, positive in sum at every node), then normalised over the
+    bodies.  The voxel pitch is the column norms of ``drr``'s affine.
+
+    ``forward`` renders the deformed volume through ``drr`` with the arguments and on the routes of a ``DRR``
+    whose own ``density`` requires a gradient; ``drr``'s own volume is read, never written.  A body is held still
+    in the ordinary torch way: a mask on the gradient, or a parameter left out of the optimiser."""
+
+    def __init__(self, drr, weights: torch.Tensor, padding: str = "zeros"):
+        super().__init__()
+        if padding not in _PADDING:
+            raise ValueError(f"padding must be 'zeros' or 'border', not {padding!r}")
+        shape = tuple(drr.density.shape)
+        if not torch.is_tensor(weights) or weights.dim() != 4 or weights.shape[0] < 1:
+            raise ValueError("weights must be a tensor of shape (K, Gx, Gy, Gz) with K >= 1, got "
+                             f"{tuple(weights.shape) if torch.is_tensor(weights) else type(weights).__name__}")
+        grid = tuple(weights.shape[1:])
+        if any(g < 2 or g > d for g, d in zip(grid, shape)):
+            raise ValueError(f"the weights' lattice must have 2 <= G_a <= D_a nodes per axis, got {grid} for a "
+                             f"volume of {shape}")
+        weights = weights.detach().to(torch.float32)
+        if not bool(torch.isfinite(weights).all()):
+            raise ValueError("weights must be finite")
+        if bool((weights < 0).any()):
+            raise ValueError("weights must be non-negative")
+        total = weights.sum(0, keepdim=True)
+        if not bool((total > 0).all()):
+            raise ValueError("weights must have a positive sum over the bodies at every node")
+        if drr.density.dtype != torch.float32:
+            raise ValueError(f"a float32 volume expected, got {drr.density.dtype}")
+        self.drr = drr
+        self.padding = padding
+        dev = drr.density.device
+        affine = drr._affine.reshape(-1, 4, 4)[0, :3, :3]
+        self.pitch = tuple(float(h) for h in affine.norm(dim=0))
+        self.register_buffer("weights", (weights / total).to(dev).contiguous())
+        K = weights.shape[0]
+        self.rotation = nn.Parameter(torch.zeros(K, 3, dtype=torch.float32, device=dev))
+        self.translation = nn.Parameter(torch.zeros(K, 3, dtype=torch.float32, device=dev))
+
+    def twists(self) -> torch.Tensor:
+        """theta (K, 6) = (rotation, translation)."""
+        return torch.cat((self.rotation, self.translation), dim=1)
+
+    def warped(self) -> torch.Tensor:
+        """The deformed volume (the shape of ``drr``'s)."""
+        return polyrigid_warp(self.drr.density, self.twists(), self.weights, self.pitch, self.padding)
+
+    def forward(self, *pose_args, **kwargs):
+        buffers = self.drr._buffers
+        theirs = buffers["density"]
+        buffers["density"] = self.warped()
+        try:
+            return self.drr(*pose_args, **kwargs)
+        finally:
+            buffers["density"] = theirs
+
+
+# ------------------------------------------------------------------------------------------------ weights
+def weights_from_labels(labels: torch.Tensor, groups, grid, sigma: float = 1.0, background: bool = True,
+                        floor: float = 1e-3) -> torch.Tensor:
+    """Lattice weights (K, Gx, Gy, Gz), float32, from an integer label map (Dx, Dy, Dz): for each group of label
+    ids (an id, or a sequence of ids) the occupancy of the map is pooled to the ``grid`` (adaptive average: the
+    share of a node's voxels that belong to the group) and blurred with a separable Gaussian of ``sigma`` nodes
+    (replicate padding).  With ``background`` a last body takes what no group claims, ``max(1 - sum, floor)``;
+    without it every node must be claimed by some group.  Normalised over the bodies."""
+    import torch.nn.functional as F
+
+    if labels.dim() != 3 or labels.dtype.is_floating_point:
+        raise ValueError("an integer label map of shape (Dx, Dy, Dz) expected")
+    grid = tuple(int(g) for g in grid)
+    if len(grid) != 3 or any(g < 2 or g > d for g, d in zip(grid, labels.shape)):
+        raise ValueError(f"grid must be (Gx, Gy, Gz) with 2 <= G_a <= D_a, got {grid} for a map of {tuple(labels.shape)}")
+    if not sigma >= 0 or not floor > 0:
+        raise ValueError("sigma >= 0 and floor > 0 expected")
+    bodies = []
+    for ids in groups:
+        ids = torch.as_tensor([ids] if isinstance(ids, int) else list(ids), device=labels.device)
+        occupancy = torch.isin(labels, ids).to(torch.float32)
+        bodies.append(F.adaptive_avg_pool3d(occupancy[None, None], grid)[0, 0])
+    w = torch.stack(bodies)
+    if sigma > 0:
+        r = max(1, int(math.ceil(3 * sigma)))
+        taps = torch.exp(-0.5 * (torch.arange(-r, r + 1, dtype=torch.float32, device=labels.device) / sigma) ** 2)
+        taps = taps / taps.sum()
+        for axis in range(3):
+            w = w.movedim(axis + 1, -1)
+            lead = w.shape
+            w = F.conv1d(F.pad(w.reshape(-1, 1, lead[-1]), (r, r), mode="replicate"), taps.reshape(1, 1, -1))
+            w = w.reshape(lead).movedim(-1, axis + 1)
+    if background:
+        w = torch.cat((w, (1 - w.sum(0, keepdim=True)).clamp(min=floor)))
+    total = w.sum(0, keepdim=True)
+    if not bool((total > 0).all()):
+        raise ValueError("a node is claimed by no group: pass background=True")
+    return (w / total).contiguous()
