@@ -5,7 +5,8 @@
 // of tens of voxels would, summed in float, leave u an ulp or two of |u| uncertain (1e-6 voxel), and floor(u)
 // decides on which side of a voxel face a sample falls -- where the coefficient gradient jumps.  floor and
 // fraction are taken from the double and only the fraction is rounded to float.  Everything after that (the
-// interpolation, every sum of the gradients) is float.  The lattice geometry and everything about sampling (Axis,
+// interpolation, every sum of the gradients) is float, but for the accumulators of the second and third gathers
+// (gather_axis).  The lattice geometry and everything about sampling (Axis,
 // axis_of, the corners) are warp_core.h's.  Host and device (DDRR_HD): tests/emu/bspline_emu.cpp compiles the
 // same functions for the CPU.
 #pragma once
@@ -233,20 +234,22 @@ DDRR_HD float node_chain(const float *q, const float *wz, int D, int G, int n, i
 }
 
 // the chain of node m of an axis of D voxels and G nodes over src[x * stride], x ascending (the second and
-// third gathers)
+// third gathers).  The sum is kept in double and rounded once: on an axis of 65535 voxels and few nodes a node's
+// chain has tens of thousands of terms, and a float accumulator loses 6e-6 of the gradient's scale there.  The
+// order stays fixed; the two gather launches are a few thousand outputs each.
 DDRR_HD float gather_axis(const float *src, long stride, int D, int G, int m) {
     const int c0 = m - 2 < 0 ? 0 : m - 2, c1 = m + 1 > G - 2 ? G - 2 : m + 1;
-    float acc = 0.f;
+    double acc = 0.0;
     for (int c = c0; c <= c1; ++c) {
         const int k = m + 1 - c, e = cell_begin(c + 1, D, G);
         for (int x = cell_begin(c, D, G); x < e; ++x) {
             float w[4];
             weights(frac_in(x, c, D, G), w);
             fold(c, G, w);
-            acc += w[k] * src[x * stride];
+            acc += (double)w[k] * (double)src[x * stride];
         }
     }
-    return acc;
+    return (float)acc;
 }
 
 // ------------------------------------------------------------------------------------------------ volume gradient

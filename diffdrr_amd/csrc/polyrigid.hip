@@ -44,7 +44,8 @@ int finish(const char *where) {
     return 0;
 }
 
-__global__ __launch_bounds__(kBlock) void forward_kernel(const float *__restrict__ V, Geometry g,
+// (4 waves per SIMD: the sample position in double fits 128 VGPRs without scratch)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void forward_kernel(const float *__restrict__ V, Geometry g,
                                                          const float *__restrict__ Xi, int padding,
                                                          float *__restrict__ W, int nq, int vec) {
     const unsigned t = blockIdx.x * (unsigned)kBlock + threadIdx.x;

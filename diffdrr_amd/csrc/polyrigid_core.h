@@ -1,7 +1,11 @@
 // polyrigid_core.h -- the arithmetic of the polyrigid deformation kernels (polyrigid.hip;
 // include/diffdrr_polyrigid_hip.h has the definitions): the twist from the cell's 8 lattice nodes, A, B, C and
 // their derivatives in s, the displacement exp(xi) y - y and its adjoint in xi, and a voxel's share of its cell's
-// 48 sums.  The lattice geometry, everything about sampling (Axis, axis_of, the corners), the pieces and the
+// 48 sums.  The sample position is formed in double (the twist at the voxel, A, B, C, exp(xi) y - y), floor and
+// fraction are taken from the double and only the fraction is rounded to float, as bspline_core.h does and for its
+// reason: floor(u) decides on which side of a voxel face a sample falls, where the twist gradient jumps, and u is
+// a difference of terms of |omega| |y| -- hundreds of mm on a long axis -- that float knows to 1e-5 mm at best.
+// Everything after that (the interpolation, the adjoint, every sum) is float.  The lattice geometry, everything about sampling (Axis, axis_of, the corners), the pieces and the
 // fixed-order sums are warp_core.h's.  Host and device (DDRR_HD): tests/emu/polyrigid_emu.cpp compiles the same
 // functions for the CPU.
 #pragma once
@@ -64,10 +68,16 @@ inline const char *domain_error(const Geometry &g, int padding) {
 }
 
 // ------------------------------------------------------------------------------------------------ the twist
-DDRR_HD float lerp(float a, float b, float t) { return a + t * (b - a); }
+DDRR_HD double lerp(double a, double b, double t) { return a + t * (b - a); }
+
+// frac_in in double: the same exact integer numerator, one division
+DDRR_HD double frac_of(int x, int c, int D, int G) {
+    return (double)((unsigned)x * (unsigned)(G - 1) - (unsigned)c * (unsigned)(D - 1)) / (double)(D - 1);
+}
 
 // the six components on the lattice line (cx + tx, cy + ty, node k): along x, then along y; 24 lattice reads
-DDRR_HD void twist_line(const float *Xi, const int G[3], int cx, int cy, float tx, float ty, int k, float L[kTwist]) {
+DDRR_HD void twist_line(const float *Xi, const int G[3], int cx, int cy, double tx, double ty, int k,
+                        double L[kTwist]) {
     const long plane = (long)G[1] * G[2], all = plane * G[0];
     const long o = (long)cx * plane + (long)cy * G[2] + k;
 #pragma unroll
@@ -78,37 +88,39 @@ DDRR_HD void twist_line(const float *Xi, const int G[3], int cx, int cy, float t
 }
 
 // ------------------------------------------------------------------------------------------------ A, B, C
-struct Coef {
-    float A, B, C, dA, dB, dC;  // and d / d s
+template <typename T>
+struct CoefOf {
+    T A, B, C, dA, dB, dC;  // and d / d s
 };
+using Coef = CoefOf<float>;
 
-constexpr float inverse_factorial(int m) {
+constexpr double inverse_factorial(int m) {
     double f = 1.0;
     for (int i = 2; i <= m; ++i) f *= i;
-    return (float)(1.0 / f);
+    return 1.0 / f;
 }
 
 // sum_n (-s)^n / (2n + First)! and its derivative in s, kTerms terms, by Horner's rule in q = -s:
 // v <- c_n + q v, and d <- v + q d is its derivative in q
-template <int First, int N = kTerms - 2>
+template <typename T, int First, int N = kTerms - 2>
 struct Series {
-    static DDRR_HD void step(float s, float &v, float &d) {
-        constexpr float c = inverse_factorial(2 * N + First);
+    static DDRR_HD void step(T s, T &v, T &d) {
+        constexpr T c = (T)inverse_factorial(2 * N + First);
         d = v - s * d;
         v = c - s * v;
-        Series<First, N - 1>::step(s, v, d);
+        Series<T, First, N - 1>::step(s, v, d);
     }
 };
-template <int First>
-struct Series<First, -1> {
-    static DDRR_HD void step(float, float &, float &) {}
+template <typename T, int First>
+struct Series<T, First, -1> {
+    static DDRR_HD void step(T, T &, T &) {}
 };
 
-template <int First>
-DDRR_HD void series(float s, float &value, float &slope) {
-    constexpr float last = inverse_factorial(2 * (kTerms - 1) + First);
-    float v = last, d = 0.f;
-    Series<First>::step(s, v, d);
+template <int First, typename T>
+DDRR_HD void series(T s, T &value, T &slope) {
+    constexpr T last = (T)inverse_factorial(2 * (kTerms - 1) + First);
+    T v = last, d = T(0);
+    Series<T, First>::step(s, v, d);
     value = v;
     slope = -d;
 }
@@ -131,37 +143,65 @@ DDRR_HD Coef coefficients(float s) {
     return k;
 }
 
+// A, B, C alone, in double (the sample position's); the seam is where the float s falls, as in coefficients
+DDRR_HD void coefficients(double s, double &A, double &B, double &C) {
+    if ((float)s < kSeriesBelow) {
+        double slope;
+        series<1>(s, A, slope);
+        series<2>(s, B, slope);
+        series<3>(s, C, slope);
+    } else {
+        const double phi = sqrt(s), sn = sin(phi);
+        A = sn / phi;
+        B = (1.0 - cos(phi)) / s;
+        C = (phi - sn) / (s * phi);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ displacement
-DDRR_HD void cross(const float a[3], const float b[3], float r[3]) {
+template <typename T>
+DDRR_HD void cross(const T a[3], const T b[3], T r[3]) {
     r[0] = a[1] * b[2] - a[2] * b[1];
     r[1] = a[2] * b[0] - a[0] * b[2];
     r[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-DDRR_HD float dot(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// mm from the volume's centre
-DDRR_HD void centred(const Geometry &g, int x, int y, int z, float out[3]) {
-    const int xs[3] = {x, y, z};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[a] = g.h[a] * ((float)xs[a] - 0.5f * (float)(g.s.D[a] - 1));
+template <typename T>
+DDRR_HD T dot(const T a[3], const T b[3]) {
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
 }
 
-// u in voxels of each axis, from the twist xi at the voxel and its position y (mm)
-DDRR_HD void displacement(const Geometry &g, const float xi[kTwist], const float y[3], float u[3]) {
-    const float *w = xi, *v = xi + 3;
-    const Coef k = coefficients(dot(w, w));
-    float a[3], b[3], wa[3], wb[3], wwb[3];
+// mm from the volume's centre (exact in double)
+DDRR_HD void centred(const Geometry &g, int x, int y, int z, double out[3]) {
+    const int xs[3] = {x, y, z};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[a] = (double)g.h[a] * ((double)xs[a] - 0.5 * (double)(g.s.D[a] - 1));
+}
+
+// u in voxels of each axis, from the twist xi at the voxel and its position y (mm), in double
+DDRR_HD void displacement(const Geometry &g, const double xi[kTwist], const double y[3], double u[3]) {
+    const double *w = xi, *v = xi + 3;
+    double A, B, C;
+    coefficients(dot(w, w), A, B, C);
+    double a[3], b[3], wa[3], wb[3], wwb[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        a[i] = k.A * y[i] + k.B * v[i];
-        b[i] = k.B * y[i] + k.C * v[i];
+        a[i] = A * y[i] + B * v[i];
+        b[i] = B * y[i] + C * v[i];
     }
     cross(w, a, wa);
     cross(w, b, wb);
     cross(w, wb, wwb);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) u[i] = ((wa[i] + wwb[i]) + v[i]) / g.h[i];
+    for (int i = 0; i < 3; ++i) u[i] = ((wa[i] + wwb[i]) + v[i]) / (double)g.h[i];
+}
+
+// one axis of a sample position from the displacement in double: clamped as axis_of clamps, floor taken here and
+// kept -- a fraction that rounds to 1 as a float stays in its voxel at f = 1, with that voxel's forward difference
+DDRR_HD Axis axis_from(int x, double u, int D, int padding) {
+    u = fmin(fmax(u, -(double)(D + 2)), (double)(D + 2));  // (a NaN: below the volume, as in axis_of)
+    const double fl = floor(u);
+    return ddrr_warp::axis_at(x + (int)fl, (float)(u - fl), D, padding);
 }
 
 // out[c] = sum_a gu[a] d u_a / d xi_c, gu the gradient in u (voxels)
@@ -201,22 +241,28 @@ DDRR_HD void twist_gradient(const Geometry &geo, const float xi[kTwist], const f
 
 // ------------------------------------------------------------------------------------------------ sampling
 // the sample position's three axes of voxel (x, y, z) from its two lattice lines L0 (node cz), L1 (cz + 1);
-// xi and y are left for the adjoint
-DDRR_HD void sample_axes(const Geometry &g, int x, int y, int z, float tz, const float L0[kTwist],
-                         const float L1[kTwist], int padding, float xi[kTwist], float pos[3], Axis ax[3]) {
+// xi and y are left, rounded to float, for the adjoint
+DDRR_HD void sample_axes(const Geometry &g, int x, int y, int z, double tz, const double L0[kTwist],
+                         const double L1[kTwist], int padding, float xi[kTwist], float pos[3], Axis ax[3]) {
+    double xd[kTwist], yd[3], u[3];
 #pragma unroll
-    for (int c = 0; c < kTwist; ++c) xi[c] = lerp(L0[c], L1[c], tz);
-    centred(g, x, y, z, pos);
-    float u[3];
-    displacement(g, xi, pos, u);
+    for (int c = 0; c < kTwist; ++c) {
+        xd[c] = lerp(L0[c], L1[c], tz);
+        xi[c] = (float)xd[c];
+    }
+    centred(g, x, y, z, yd);
+    displacement(g, xd, yd, u);
     const int xs[3] = {x, y, z};
 #pragma unroll
-    for (int a = 0; a < 3; ++a) ax[a] = axis_of(xs[a], u[a], g.s.D[a], padding);
+    for (int a = 0; a < 3; ++a) {
+        pos[a] = (float)yd[a];
+        ax[a] = axis_from(xs[a], u[a], g.s.D[a], padding);
+    }
 }
 
 // W of one voxel
-DDRR_HD float warp_voxel(const float *V, const Geometry &g, int x, int y, int z, float tz, const float L0[kTwist],
-                         const float L1[kTwist], int padding) {
+DDRR_HD float warp_voxel(const float *V, const Geometry &g, int x, int y, int z, double tz, const double L0[kTwist],
+                         const double L1[kTwist], int padding) {
     Axis ax[3];
     float xi[kTwist], pos[3];
     sample_axes(g, x, y, z, tz, L0, L1, padding, xi, pos, ax);
@@ -234,17 +280,21 @@ DDRR_HD float warp_voxel(const float *V, const Geometry &g, int x, int y, int z,
 DDRR_HD void forward_run(const float *V, const Geometry &g, const float *Xi, int padding, int x, int y, int z0,
                          float out[4]) {
     const Shape &s = g.s;
-    const Cell cx = cell_of(x, s.D[0], s.G[0]), cy = cell_of(y, s.D[1], s.G[1]);
-    float L0[kTwist], L1[kTwist];
+    const int cx = cell_of(x, s.D[0], s.G[0]).c, cy = cell_of(y, s.D[1], s.G[1]).c;
+    const double tx = frac_of(x, cx, s.D[0], s.G[0]), ty = frac_of(y, cy, s.D[1], s.G[1]);
+    double L0[kTwist], L1[kTwist];
     int c = cell_of(z0, s.D[2], s.G[2]).c;
     unsigned r = (unsigned)z0 * (unsigned)(s.G[2] - 1) - (unsigned)c * (unsigned)(s.D[2] - 1);
-    twist_line(Xi, s.G, cx.c, cy.c, cx.t, cy.t, c, L0);
-    twist_line(Xi, s.G, cx.c, cy.c, cx.t, cy.t, c + 1, L1);
-    const float den = (float)(s.D[2] - 1);
+    twist_line(Xi, s.G, cx, cy, tx, ty, c, L0);
+    twist_line(Xi, s.G, cx, cy, tx, ty, c + 1, L1);
+    const double den = (double)(s.D[2] - 1);
 #pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = 0.f;
+    // (not unrolled: one voxel's double arithmetic at a time keeps the kernel at 4 waves per SIMD without scratch;
+    // the result goes to out[k] through selects, so that out stays in registers)
+#pragma unroll 1
     for (int k = 0; k < 4; ++k) {
         const int z = z0 + k;
-        out[k] = 0.f;
         if (z < s.D[2]) {
             if (k > 0) {
                 r += (unsigned)(s.G[2] - 1);
@@ -253,10 +303,12 @@ DDRR_HD void forward_run(const float *V, const Geometry &g, const float *Xi, int
                     ++c;
 #pragma unroll
                     for (int a = 0; a < kTwist; ++a) L0[a] = L1[a];
-                    twist_line(Xi, s.G, cx.c, cy.c, cx.t, cy.t, c + 1, L1);
+                    twist_line(Xi, s.G, cx, cy, tx, ty, c + 1, L1);
                 }
             }
-            out[k] = warp_voxel(V, g, x, y, z, (float)r / den, L0, L1, padding);
+            const float w = warp_voxel(V, g, x, y, z, (double)r / den, L0, L1, padding);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = e == k ? w : out[e];
         }
     }
 }
@@ -264,11 +316,11 @@ DDRR_HD void forward_run(const float *V, const Geometry &g, const float *Xi, int
 // ------------------------------------------------------------------------------------------------ twist gradient
 // what voxel (x, y, z) of a cell adds to the cell's 48 sums: acc[6 n + c] += hat_n gW sum_a d_a V(p) d u_a / d xi_c
 DDRR_HD void accumulate_voxel(const float *V, const Geometry &g, int x, int y, int z, const float wxy[4], float tz,
-                              const float L0[kTwist], const float L1[kTwist], int padding, float gw,
+                              double tzd, const double L0[kTwist], const double L1[kTwist], int padding, float gw,
                               float acc[kPieceFloats]) {
     Axis ax[3];
     float xi[kTwist], pos[3];
-    sample_axes(g, x, y, z, tz, L0, L1, padding, xi, pos, ax);
+    sample_axes(g, x, y, z, tzd, L0, L1, padding, xi, pos, ax);
     long o[8];
     corner_offsets(g.s.D, ax[0], ax[1], ax[2], o);
     float v[8], gu[3], gxi[kTwist];
@@ -307,13 +359,15 @@ DDRR_HD void piece_thread(const float *V, const Geometry &g, const float *Xi, in
         const unsigned lx = row / (unsigned)box.n[1];
         const int y = box.b[1] + (int)(row - lx * (unsigned)box.n[1]);
         const int x = box.b[0] + (int)lx;
-        const float tx = frac_in(x, cx, s.D[0], s.G[0]), ty = frac_in(y, cy, s.D[1], s.G[1]);
-        float wxy[4], L0[kTwist], L1[kTwist];
-        column_weights(tx, ty, wxy);
+        float wxy[4];
+        double L0[kTwist], L1[kTwist];
+        column_weights(frac_in(x, cx, s.D[0], s.G[0]), frac_in(y, cy, s.D[1], s.G[1]), wxy);
+        const double tx = frac_of(x, cx, s.D[0], s.G[0]), ty = frac_of(y, cy, s.D[1], s.G[1]);
         twist_line(Xi, s.G, cx, cy, tx, ty, cz, L0);
         twist_line(Xi, s.G, cx, cy, tx, ty, cz + 1, L1);
         const long at = ((long)x * s.D[1] + y) * s.D[2] + z;
-        accumulate_voxel(V, g, x, y, z, wxy, frac_in(z, cz, s.D[2], s.G[2]), L0, L1, padding, gW[at], acc);
+        accumulate_voxel(V, g, x, y, z, wxy, frac_in(z, cz, s.D[2], s.G[2]), frac_of(z, cz, s.D[2], s.G[2]), L0, L1,
+                         padding, gW[at], acc);
     }
 }
 
@@ -341,12 +395,14 @@ DDRR_HD float twist_node_sum(const float *ws, const Shape &s, long pieces, int c
 DDRR_HD void scatter_terms(const Geometry &g, const float *Xi, int padding, int x, int y, int z, float gw, long o[8],
                            float w[8]) {
     const Shape &s = g.s;
-    const Cell cx = cell_of(x, s.D[0], s.G[0]), cy = cell_of(y, s.D[1], s.G[1]), cz = cell_of(z, s.D[2], s.G[2]);
-    float L0[kTwist], L1[kTwist], xi[kTwist], pos[3];
-    twist_line(Xi, s.G, cx.c, cy.c, cx.t, cy.t, cz.c, L0);
-    twist_line(Xi, s.G, cx.c, cy.c, cx.t, cy.t, cz.c + 1, L1);
+    const int cx = cell_of(x, s.D[0], s.G[0]).c, cy = cell_of(y, s.D[1], s.G[1]).c, cz = cell_of(z, s.D[2], s.G[2]).c;
+    const double tx = frac_of(x, cx, s.D[0], s.G[0]), ty = frac_of(y, cy, s.D[1], s.G[1]);
+    double L0[kTwist], L1[kTwist];
+    float xi[kTwist], pos[3];
+    twist_line(Xi, s.G, cx, cy, tx, ty, cz, L0);
+    twist_line(Xi, s.G, cx, cy, tx, ty, cz + 1, L1);
     Axis ax[3];
-    sample_axes(g, x, y, z, cz.t, L0, L1, padding, xi, pos, ax);
+    sample_axes(g, x, y, z, frac_of(z, cz, s.D[2], s.G[2]), L0, L1, padding, xi, pos, ax);
     // an axis whose two corners are one voxel (clamped at a face of the volume) scatters their weights as one term:
     // the motions here throw whole regions out of the volume, and with border padding a face voxel would take two,
     // four or eight separately rounded adds from each such sample

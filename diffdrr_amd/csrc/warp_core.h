@@ -113,13 +113,8 @@ struct Axis {
     float w0, w1, d0, d1;
 };
 
-// p = x + u is never rounded to a float: floor(p) = x + floor(u) and f = u - floor(u) carry the precision of
-// u (a few voxels), not of p (up to D), which is what decides on which side of a voxel face a sample falls
-DDRR_HD Axis axis_of(int x, float u, int D, int padding) {
-    u = fminf(fmaxf(u, -(float)(D + 2)), (float)(D + 2));  // (beyond: outside the volume anyway; a NaN: below it)
-    const float fl = floorf(u);
-    const int i = x + (int)fl;
-    const float f = u - fl;
+// the axis of a sample at voxel i + f, 0 <= f <= 1
+DDRR_HD Axis axis_at(int i, float f, int D, int padding) {
     const bool border = padding == DDRR_WARP_PADDING_BORDER;
     const float m0 = (border || (i >= 0 && i < D)) ? 1.f : 0.f;
     const float m1 = (border || (i + 1 >= 0 && i + 1 < D)) ? 1.f : 0.f;
@@ -131,6 +126,14 @@ DDRR_HD Axis axis_of(int x, float u, int D, int padding) {
     r.d0 = -m0;
     r.d1 = m1;
     return r;
+}
+
+// p = x + u is never rounded to a float: floor(p) = x + floor(u) and f = u - floor(u) carry the precision of
+// u (a few voxels), not of p (up to D), which is what decides on which side of a voxel face a sample falls
+DDRR_HD Axis axis_of(int x, float u, int D, int padding) {
+    u = fminf(fmaxf(u, -(float)(D + 2)), (float)(D + 2));  // (beyond: outside the volume anyway; a NaN: below it)
+    const float fl = floorf(u);
+    return axis_at(x + (int)fl, u - fl, D, padding);
 }
 
 // the 8 corners' offsets into the volume, [4 i + 2 j + k], in 64 bits; always inside it

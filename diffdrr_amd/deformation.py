@@ -28,9 +28,20 @@ def _check_basis(basis):
 
 
 # ------------------------------------------------------------------------------------------------ definition
-def _cells(D: int, G: int, device, dtype):
+def _span(D, box, axis):
+    """The voxels of an axis a definition is evaluated at: all of them, or ``box[axis] = (start, stop)``."""
+    if box is None:
+        return 0, int(D)
+    start, stop = (int(v) for v in box[axis])
+    if not 0 <= start < stop <= int(D):
+        raise ValueError(f"box must be three (start, stop) ranges inside the volume, got {tuple(box[axis])} on axis "
+                         f"{axis} of {int(D)} voxels")
+    return start, stop
+
+
+def _cells(D: int, G: int, device, dtype, span=None):
     """Cell and fraction of every voxel of an axis (include/diffdrr_warp_hip.h): integers, then one division."""
-    num = torch.arange(D, device=device) * (G - 1)
+    num = torch.arange(*(span or (0, D)), device=device) * (G - 1)
     c = torch.div(num, D - 1, rounding_mode="floor").clamp(max=G - 2)
     return c, (num - c * (D - 1)).to(dtype) / (D - 1)
 
@@ -40,17 +51,18 @@ def bspline_weights(t: torch.Tensor):
     return ((1 - t) ** 3 / 6, (3 * t ** 3 - 6 * t ** 2 + 4) / 6, (-3 * t ** 3 + 3 * t ** 2 + 3 * t + 1) / 6, t ** 3 / 6)
 
 
-def dense_field(displacement: torch.Tensor, shape, basis: str = "linear") -> torch.Tensor:
+def dense_field(displacement: torch.Tensor, shape, basis: str = "linear", box=None) -> torch.Tensor:
     """u (3, Dx, Dy, Dz): the lattice ``displacement`` (3, Gx, Gy, Gz) evaluated at every voxel, node i of axis a
     at voxel coordinate i (D_a - 1) / (G_a - 1): interpolated trilinearly (``basis="linear"``), or the cubic
     B-spline with these coefficients (``basis="bspline"``: per axis the four weights of the voxel's fraction on
     the coefficients c - 1 .. c + 2 of its cell c, indices clamped to the lattice; an approximating spline --
-    the field at a node is not the node's coefficient)."""
+    the field at a node is not the node's coefficient).  ``box``, three (start, stop) voxel ranges: the field on
+    those voxels only, (3, x1 - x0, y1 - y0, z1 - z0) -- what the whole field holds there."""
     _check_basis(basis)
     u = displacement
     for axis, D in enumerate(shape):
         G = u.shape[axis + 1]
-        c, t = _cells(int(D), G, u.device, u.dtype)
+        c, t = _cells(int(D), G, u.device, u.dtype, _span(D, box, axis))
         t = t.reshape([-1 if d == axis + 1 else 1 for d in range(4)])
         if basis == "linear":
             u = (1 - t) * u.index_select(axis + 1, c) + t * u.index_select(axis + 1, c + 1)
@@ -59,67 +71,87 @@ def dense_field(displacement: torch.Tensor, shape, basis: str = "linear") -> tor
     return u
 
 
-def sample_coordinates(displacement: torch.Tensor, shape, basis: str = "linear") -> torch.Tensor:
-    """p (3, Dx, Dy, Dz) = x + u(x), clamped to [-2, D_a + 1] (which changes no sample)."""
-    u = dense_field(displacement, shape, basis)
+def sample_coordinates(displacement: torch.Tensor, shape, basis: str = "linear", box=None) -> torch.Tensor:
+    """p (3, Dx, Dy, Dz) = x + u(x), clamped to [-2, D_a + 1] (which changes no sample); with ``box`` on its voxels
+    only (see :func:`dense_field`)."""
+    u = dense_field(displacement, shape, basis, box)
     p = []
     for a, D in enumerate(shape):
-        x = torch.arange(int(D), device=u.device, dtype=u.dtype).reshape([-1 if d == a else 1 for d in range(3)])
+        x = torch.arange(*_span(D, box, a), device=u.device, dtype=u.dtype).reshape(
+            [-1 if d == a else 1 for d in range(3)])
         p.append((x + u[a]).clamp(-2.0, float(D) + 1.0))
     return torch.stack(p)
 
 
-def _trilinear(volume, pairs, padding):
-    """sum over the 8 corners of w_c V[i0 + c] from the per-axis (floor, fraction) ``pairs``."""
+def _trilinear(volume, pairs, padding, part=None):
+    """sum over the 8 corners of w_c V[i0 + c] from the per-axis (floor, fraction) ``pairs``.  The voxels are
+    gathered from ``volume`` as it is and cast to the weights' dtype after the gather.  ``part`` = (shape, three
+    (start, stop) ranges): ``volume`` holds only those ranges of a volume of ``shape``, and every voxel the
+    samples reach must lie in them."""
+    shape, held = (volume.shape, None) if part is None else part
     axes = []
-    for D, (i, f) in zip(volume.shape, pairs):
+    for a, (D, (i, f)) in enumerate(zip(shape, pairs)):
         pair = []
         for idx, w in ((i, 1 - f), (i + 1, f)):
             if padding == "zeros":
                 w = w * ((idx >= 0) & (idx < D)).to(w.dtype)
-            pair.append((idx.clamp(0, D - 1), w))
+            idx = idx.clamp(0, int(D) - 1)
+            if held is not None:
+                start, stop = (int(v) for v in held[a])
+                if stop - start != volume.shape[a] or int(idx.min()) < start or int(idx.max()) >= stop:
+                    raise ValueError(f"axis {a}: the samples reach voxels {int(idx.min())} .. {int(idx.max())}, the "
+                                     f"part of the volume given is {start} .. {stop - 1} ({volume.shape[a]} voxels)")
+                idx = idx - start
+            pair.append((idx, w))
         axes.append(pair)
     out = 0
     for ix, wx in axes[0]:
         for iy, wy in axes[1]:
             for iz, wz in axes[2]:
-                out = out + wx * wy * wz * volume[ix, iy, iz]
+                out = out + wx * wy * wz * volume[ix, iy, iz].to(wz.dtype)
     return out
 
 
-def sample_displaced(volume: torch.Tensor, u: torch.Tensor, padding: str = "zeros") -> torch.Tensor:
+def sample_displaced(volume: torch.Tensor, u: torch.Tensor, padding: str = "zeros", box=None,
+                     part=None) -> torch.Tensor:
     """``V(x + u(x))`` for a dense field ``u`` (3, Dx, Dy, Dz) in voxels, trilinear.  floor(p) = x + floor(u) and
     f = u - floor(u) are formed from u, as the kernels form them: they carry the precision of u (a few voxels),
-    not that of p = x + u (up to D).  u_a is clamped to [-(D_a + 2), D_a + 2] first (which changes no sample)."""
+    not that of p = x + u (up to D).  u_a is clamped to [-(D_a + 2), D_a + 2] first (which changes no sample).
+
+    ``box``, three (start, stop) voxel ranges: ``u`` is the field on those voxels only and so is the result.
+    ``part`` = (shape, three (start, stop) ranges): ``volume`` is only that part of a volume of ``shape`` (for a
+    box of a volume too large to copy or to take a gradient of); it must hold every voxel the samples reach."""
+    shape = volume.shape if part is None else part[0]
     pairs = []
-    for a, D in enumerate(volume.shape):
+    for a, D in enumerate(shape):
         ua = u[a].clamp(-(float(D) + 2.0), float(D) + 2.0)
         fl = ua.detach().floor()
-        x = torch.arange(int(D), device=u.device).reshape([-1 if d == a else 1 for d in range(3)])
+        x = torch.arange(*_span(D, box, a), device=u.device).reshape([-1 if d == a else 1 for d in range(3)])
         pairs.append((x + fl.long(), ua - fl))
-    return _trilinear(volume, pairs, padding)
+    return _trilinear(volume, pairs, padding, part)
 
 
 def warp_reference(volume: torch.Tensor, displacement: torch.Tensor, padding: str = "zeros",
-                   basis: str = "linear") -> torch.Tensor:
-    """The definition of :func:`warp_volume` by torch indexing, in the dtype of its arguments and on their
-    device; autograd gives both gradients (``floor`` has none: at f = 0 the derivative is the forward
-    difference).  ``basis``: see :func:`dense_field`."""
+                   basis: str = "linear", box=None, part=None) -> torch.Tensor:
+    """The definition of :func:`warp_volume` by torch indexing, in the dtype of the lattice and on the
+    arguments' device; autograd gives both gradients (``floor`` has none: at f = 0 the derivative is the forward
+    difference).  ``basis``: see :func:`dense_field`; ``box`` and ``part``: see :func:`sample_displaced`."""
     if padding not in _PADDING:
         raise ValueError(f"padding must be 'zeros' or 'border', not {padding!r}")
     _check_basis(basis)
-    if volume.dim() != 3 or displacement.dim() != 4 or displacement.shape[0] != 3:
+    shape = volume.shape if part is None else part[0]
+    if volume.dim() != 3 or len(shape) != 3 or displacement.dim() != 4 or displacement.shape[0] != 3:
         raise ValueError("a (Dx, Dy, Dz) volume and a (3, Gx, Gy, Gz) lattice expected")
-    if any(g < 2 or g > d for g, d in zip(displacement.shape[1:], volume.shape)):
+    if any(g < 2 or g > d for g, d in zip(displacement.shape[1:], shape)):
         raise ValueError("the lattice needs 2 <= G_a <= D_a nodes per axis")
     if basis == "bspline":  # (the linear basis rounds p itself, as it always has)
-        return sample_displaced(volume, dense_field(displacement, volume.shape, basis), padding)
-    p = sample_coordinates(displacement, volume.shape)
+        return sample_displaced(volume, dense_field(displacement, shape, basis, box), padding, box, part)
+    p = sample_coordinates(displacement, shape, box=box)
     pairs = []
     for a in range(3):
         fl = p[a].detach().floor()
         pairs.append((fl.long(), p[a] - fl))
-    return _trilinear(volume, pairs, padding)
+    return _trilinear(volume, pairs, padding, part)
 
 
 # ------------------------------------------------------------------------------------------------ kernels

@@ -21,18 +21,40 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from .deformation import _PADDING, dense_field, sample_displaced
+from .deformation import _PADDING, _span, dense_field, sample_displaced
 
 SERIES_BELOW, SERIES_TERMS = _lib.POLYRIGID_SERIES_BELOW, _lib.POLYRIGID_SERIES_TERMS
 
 
+class _BlendFn(torch.autograd.Function):
+    """``einsum("kxyz,kc->cxyz", weights, theta)`` whose gradient in ``theta`` is summed over the nodes in float64.
+    That sum has one term per node -- as many as voxels on a lattice as fine as the volume -- and the terms cancel:
+    about the identity on a (2, 65535, 2) lattice their magnitudes add up to 111 times the result, and a float32
+    reduction leaves 4e-5 .. 9e-5 of the gradient's scale, a different figure for every order of summation."""
+
+    @staticmethod
+    def forward(ctx, theta, weights):
+        ctx.save_for_backward(theta, weights)
+        return torch.einsum("kxyz,kc->cxyz", weights, theta)
+
+    @staticmethod
+    def backward(ctx, grad):
+        theta, weights = ctx.saved_tensors
+        g_theta = g_weights = None
+        if ctx.needs_input_grad[0]:
+            g_theta = torch.einsum("kxyz,cxyz->kc", weights.double(), grad.double()).to(theta.dtype)
+        if ctx.needs_input_grad[1]:
+            g_weights = torch.einsum("kc,cxyz->kxyz", theta, grad)
+        return g_theta, g_weights
+
+
 def twist_lattice(theta: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
     """Xi (6, Gx, Gy, Gz): ``Xi[c, n] = sum_k weights[k, n] theta[k, c]`` -- the bodies' twists ``theta`` (K, 6)
-    blended in the Lie algebra by the lattice ``weights`` (K, Gx, Gy, Gz)."""
+    blended in the Lie algebra by the lattice ``weights`` (K, Gx, Gy, Gz).  Differentiable in both."""
     if theta.dim() != 2 or theta.shape[1] != 6 or weights.dim() != 4 or weights.shape[0] != theta.shape[0]:
         raise ValueError(f"twists of shape (K, 6) and weights of shape (K, Gx, Gy, Gz) expected, got "
                          f"{tuple(theta.shape)} and {tuple(weights.shape)}")
-    return torch.einsum("kxyz,kc->cxyz", weights, theta).contiguous()
+    return _BlendFn.apply(theta, weights).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ definition
@@ -59,41 +81,45 @@ def _cross(a, b):
     return torch.stack((a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]))
 
 
-def centred_coordinates(shape, pitch, device, dtype) -> torch.Tensor:
-    """y (3, Dx, Dy, Dz): every voxel's position in mm from the volume's centre, y_a = h_a (x_a - (D_a - 1) / 2)."""
-    axes = [float(h) * (torch.arange(int(D), device=device, dtype=dtype) - 0.5 * (int(D) - 1))
-            for D, h in zip(shape, pitch)]
+def centred_coordinates(shape, pitch, device, dtype, box=None) -> torch.Tensor:
+    """y (3, Dx, Dy, Dz): every voxel's position in mm from the volume's centre, y_a = h_a (x_a - (D_a - 1) / 2);
+    with ``box``, three (start, stop) voxel ranges, of those voxels only."""
+    axes = [float(h) * (torch.arange(*_span(D, box, a), device=device, dtype=dtype) - 0.5 * (int(D) - 1))
+            for a, (D, h) in enumerate(zip(shape, pitch))]
     return torch.stack(torch.meshgrid(*axes, indexing="ij"))
 
 
-def displacement_field(twists: torch.Tensor, shape, pitch=(1.0, 1.0, 1.0)) -> torch.Tensor:
+def displacement_field(twists: torch.Tensor, shape, pitch=(1.0, 1.0, 1.0), box=None) -> torch.Tensor:
     """u (3, Dx, Dy, Dz) in voxels of each axis: the twist lattice (6, Gx, Gy, Gz) interpolated trilinearly to
-    every voxel, then ``exp(xi) y - y`` there, formed directly (include/diffdrr_polyrigid_hip.h)."""
-    xi = dense_field(twists, shape)
+    every voxel, then ``exp(xi) y - y`` there, formed directly (include/diffdrr_polyrigid_hip.h); with ``box``,
+    three (start, stop) voxel ranges, on those voxels only."""
+    xi = dense_field(twists, shape, box=box)
     w, v = xi[:3], xi[3:]
-    y = centred_coordinates(shape, pitch, xi.device, xi.dtype)
+    y = centred_coordinates(shape, pitch, xi.device, xi.dtype, box)
     A, B, C = exponential_coefficients((w * w).sum(0))
     u_mm = _cross(w, A * y + B * v) + _cross(w, _cross(w, B * y + C * v)) + v
     h = torch.tensor([float(p) for p in pitch], device=xi.device, dtype=xi.dtype).reshape(3, 1, 1, 1)
     return u_mm / h
 
 
-def _check_definition(volume, twists, padding):
+def _check_definition(volume, shape, twists, padding):
     if padding not in _PADDING:
         raise ValueError(f"padding must be 'zeros' or 'border', not {padding!r}")
-    if volume.dim() != 3 or twists.dim() != 4 or twists.shape[0] != 6:
+    if volume.dim() != 3 or len(shape) != 3 or twists.dim() != 4 or twists.shape[0] != 6:
         raise ValueError("a (Dx, Dy, Dz) volume and a (6, Gx, Gy, Gz) twist lattice expected")
-    if any(g < 2 or g > d for g, d in zip(twists.shape[1:], volume.shape)):
+    if any(g < 2 or g > d for g, d in zip(twists.shape[1:], shape)):
         raise ValueError("the lattice needs 2 <= G_a <= D_a nodes per axis")
 
 
 def polyrigid_reference(volume: torch.Tensor, theta: torch.Tensor, weights: torch.Tensor, pitch=(1.0, 1.0, 1.0),
-                        padding: str = "zeros") -> torch.Tensor:
-    """The definition of :func:`polyrigid_warp` by torch indexing, in the dtype of its arguments and on their
-    device; autograd gives every gradient (``floor`` has none: at f = 0 the derivative is the forward difference)."""
+                        padding: str = "zeros", box=None, part=None) -> torch.Tensor:
+    """The definition of :func:`polyrigid_warp` by torch indexing, in the dtype of the twists and on the
+    arguments' device; autograd gives every gradient (``floor`` has none: at f = 0 the derivative is the forward
+    difference).  ``box`` and ``part``: see :func:`diffdrr_amd.deformation.sample_displaced`."""
     twists = twist_lattice(theta, weights)
-    _check_definition(volume, twists, padding)
-    return sample_displaced(volume, displacement_field(twists, volume.shape, pitch), padding)
+    shape = volume.shape if part is None else part[0]
+    _check_definition(volume, shape, twists, padding)
+    return sample_displaced(volume, displacement_field(twists, shape, pitch, box), padding, box, part)
 
 
 # ------------------------------------------------------------------------------------------------ kernels

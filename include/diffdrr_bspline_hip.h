@@ -34,7 +34,8 @@
  *     r1[a, x, y, n] (3, Dx, Dy, Gz) = sum_z w^z_n(z) q_a(x, y, z),   q_a = gW d_a V(p),
  *     r2[a, x, m, n] (3, Dx, Gy, Gz) = sum_y w^y_m(y) r1[a, x, y, n],
  *     gU[a, l, m, n]                 = sum_x w^x_l(x) r2[a, x, m, n],
- *   each sum a chain of  acc = acc + w v  from 0 over the voxels of the cells max(n - 2, 0) .. min(n + 1, G - 2)
+ *   each sum a chain of  acc = acc + w v  from 0 (a float for r1; a double, rounded once at the end, for r2
+ *   and gU, whose chains grow with the axis: tens of thousands of terms at 65535 voxels) over the voxels of the cells max(n - 2, 0) .. min(n + 1, G - 2)
  *   of that axis in ascending voxel order; voxel x of cell c carries the weight of its tap k = n + 1 - c,
  *   folded: in cell 0 the weight of tap 0 is added to tap 1's (w_1 = B_1 + B_0), in cell G - 2 tap 3's to
  *   tap 2's (w_2 = B_2 + B_3).  The first gather walks a row in pieces of DDRR_BSPLINE_CHUNK_VOXELS voxels and

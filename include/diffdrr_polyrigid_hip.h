@@ -34,6 +34,11 @@
  *   Sampling.  That of include/diffdrr_warp_hip.h: i0 = x + floor(u), f = u - floor(u), u_a clamped to
  *     [-(D_a + 2), D_a + 2] first; eight corners; DDRR_POLYRIGID_PADDING_ZEROS or _BORDER.  Xi = 0 gives u = 0
  *     and W == V exactly.
+ *   Precision.  The sample position -- the fractions, the twist at the voxel, y, A, B, C and u -- is formed in
+ *     double from the float inputs; floor(u) is taken from the double and only f is rounded to float (an f that
+ *     rounds to 1 stays in its voxel, at f = 1).  u is a difference of terms of |omega| |y|, hundreds of mm on a
+ *     long axis, and floor(u) decides which forward difference the gradients take.  The interpolation of V, the
+ *     adjoint below (on the twist and y rounded to float) and every sum are float.
  *   Gradients for an upstream gW:
  *       gXi[c, n] = sum_x hat_n(x) sum_a gW[x] d_a V(p(x)) d u_a / d xi_c (x),   hat_n the trilinear weight of
  *                   node n at x, d_a V as in include/diffdrr_warp_hip.h (at f = 0 the forward difference);

@@ -26,7 +26,7 @@ EMU_SO = os.path.join(ROOT, "tests", "emu", "_build", "libbspline_emu.so")
 FLOOR = 1e-6
 BASIS = "bspline"
 
-# name -> (volume, lattice): warp_cases' four, and the only shape with cells whose four taps are all unclamped
+# name -> (volume, lattice): warp_cases' table, and the only shape with cells whose four taps are all unclamped
 # on every axis
 CASES = dict(warp_cases.CASES)
 CASES["37x41x45"] = ((37, 41, 45), (7, 6, 8))
@@ -95,14 +95,22 @@ def reference(V, U, gW, padding, dtype):
     return W.detach().double(), gV.double(), gU.double()
 
 
-def coefficient_gradient_scale(V, U, gW, padding):
-    """Per component a: max_n sum_x |B_n(x) gW[x] d_a V(p(x))| in float64.  q = gW dV(p) is the gradient of the
-    sampling in the dense field; B_n >= 0, so the adjoint of ``dense_field`` spreads |q| over the nodes."""
+def coefficient_gradient_spread(V, U, gW, padding, box=None, part=None):
+    """(3, Gx, Gy, Gz): sum_x |B_n(x) gW[x] d_a V(p(x))| in float64.  q = gW dV(p) is the gradient of the
+    sampling in the dense field; B_n >= 0, so the adjoint of ``dense_field`` spreads |q| over the nodes.  With
+    ``box`` and ``part`` (diffdrr_amd.deformation.sample_displaced) the sum runs over the box's voxels."""
     V, U, gW = V.double(), U.double(), gW.double()
-    u = dense_field(U, V.shape, BASIS).requires_grad_()
-    q, = torch.autograd.grad(sample_displaced(V, u, padding), u, gW)
+    shape = V.shape if part is None else part[0]
+    u = dense_field(U, shape, BASIS, box).requires_grad_()
+    q, = torch.autograd.grad(sample_displaced(V, u, padding, box, part), u, gW)
     leaf = torch.zeros_like(U).requires_grad_()
-    spread, = torch.autograd.grad((dense_field(leaf, V.shape, BASIS) * q.abs()).sum(), leaf)
+    spread, = torch.autograd.grad((dense_field(leaf, shape, BASIS, box) * q.abs()).sum(), leaf)
+    return spread
+
+
+def coefficient_gradient_scale(V, U, gW, padding):
+    """Per component a: the largest entry of :func:`coefficient_gradient_spread` over the nodes."""
+    spread = coefficient_gradient_spread(V, U, gW, padding)
     return [float(spread[a].max()) for a in range(3)]
 
 
@@ -173,8 +181,9 @@ def check_identity(case, kind, padding, device):
 
 def check_reproducible(device, ops):
     """Forward and the coefficient gradient, each run twice, agree bit for bit (rows of several chunks' worth
-    of nodes, tails, interior cells)."""
-    for case in ("40x36x130", "37x41x45"):
+    of nodes, tails, interior cells; chains that continue from one z chunk to the next, with and without
+    16-byte stores)."""
+    for case in ("40x36x130", "37x41x45", "5x6x600", "3x4x1024"):
         V, U, gW = (t.to(device) for t in scene(case, "noise", 2.5))
         for padding in PADDINGS:
             a, b = ops.bspline_forward(V, U, padding), ops.bspline_forward(V, U, padding)

@@ -194,6 +194,13 @@ int main() {
         rc |= run(5, 6, 600, 2, 3, 9, 24.f, padding);    // chains that continue across chunks
         rc |= run(2, 2, 2, 2, 2, 2, 2.5f, padding);
         rc |= run(2, 2, 2, 2, 2, 2, 24.f, padding);
+        // rows of several z chunks, a node per voxel, axes at the 65535 limit (tests/warp_cases.py)
+        rc |= run(5, 6, 600, 3, 4, 7, 24.f, padding);
+        rc |= run(6, 5, 515, 2, 5, 515, 24.f, padding);
+        rc |= run(3, 4, 1024, 3, 2, 33, 24.f, padding);
+        rc |= run(65535, 2, 3, 9, 2, 2, 24.f, padding);
+        rc |= run(3, 65535, 2, 2, 65535, 2, 24.f, padding);
+        rc |= run(2, 3, 65535, 2, 3, 700, 24.f, padding);
     }
     return rc;
 }

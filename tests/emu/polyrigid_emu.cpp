@@ -162,6 +162,13 @@ int main() {
         rc |= run(40, 36, 130, 3, 3, 5, 0.3f, 6.f, padding);
         rc |= run(2, 2, 2, 2, 2, 2, 0.05f, 1.5f, padding);
         rc |= run(2, 2, 2, 2, 2, 2, 2.f, 600.f, padding);  // (the closed forms; every sample far outside)
+        // rows of several z chunks, a node per voxel, axes at the 65535 limit (tests/warp_cases.py)
+        rc |= run(5, 6, 600, 3, 4, 7, 0.3f, 6.f, padding);
+        rc |= run(6, 5, 515, 2, 5, 515, 0.3f, 6.f, padding);
+        rc |= run(3, 4, 1024, 3, 2, 33, 0.3f, 6.f, padding);
+        rc |= run(65535, 2, 3, 9, 2, 2, 0.3f, 6.f, padding);
+        rc |= run(3, 65535, 2, 2, 65535, 2, 0.3f, 6.f, padding);
+        rc |= run(2, 3, 65535, 2, 3, 700, 0.3f, 6.f, padding);
     }
     return rc;
 }

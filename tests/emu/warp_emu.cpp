@@ -158,6 +158,13 @@ int main() {
         rc |= run(9, 10, 133, 2, 3, 17, 12.f, padding);
         rc |= run(2, 2, 2, 2, 2, 2, 2.5f, padding);
         rc |= run(2, 2, 2, 2, 2, 2, 12.f, padding);
+        // rows of several z chunks, a node per voxel, axes at the 65535 limit (tests/warp_cases.py)
+        rc |= run(5, 6, 600, 3, 4, 7, 12.f, padding);
+        rc |= run(6, 5, 515, 2, 5, 515, 12.f, padding);
+        rc |= run(3, 4, 1024, 3, 2, 33, 12.f, padding);
+        rc |= run(65535, 2, 3, 9, 2, 2, 12.f, padding);
+        rc |= run(3, 65535, 2, 2, 65535, 2, 12.f, padding);
+        rc |= run(2, 3, 65535, 2, 3, 700, 12.f, padding);
     }
     return rc;
 }

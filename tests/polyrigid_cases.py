@@ -22,12 +22,22 @@ from warp_cases import CASES, KINDS, PADDINGS, chain_scene, gate, recovery_loop,
 EMU_SRC = os.path.join(ROOT, "tests", "emu", "polyrigid_emu.cpp")
 EMU_SO = os.path.join(ROOT, "tests", "emu", "_build", "libpolyrigid_emu.so")
 PITCH = (0.8, 1.0, 2.5)
-# amplitude -> (bodies, |omega| <= . rad, |v| <= . mm)
-AMPLITUDES = {"small": (1, 0.05, 1.5), "large": (3, 0.3, 6.0)}
+# amplitude -> (bodies, |omega| <= . rad, |v| <= . mm).  "lever" bounds the rotation by LEVER_MM over the distance
+# of the volume's corners from its centre: the corners move by a few voxels whatever the shape.  The fixed bounds
+# move the ends of an axis of 65535 voxels by thousands of voxels, where one float32 ulp of the displacement
+# (5e-4 voxel at 4096) is more than the 1e-4 voxel that near_face_fraction asks of a sample's distance to a voxel
+# face: the float32 reference then guesses the side, and with border padding, where such samples still interpolate
+# along the long axis, its own error -- the gate -- is 1e-3 .. 3e-1 of scale in the lattice gradients.  The kernels
+# form the position in double, but from the float32 twist lattice, whose own rounding times such a lever is 1e-4
+# voxel: they sit at up to 9e-3 and 1.4e-1 there.  "lever" is where the gate on the long shapes is tight.
+AMPLITUDES = {"small": (1, 0.05, 1.5), "large": (3, 0.3, 6.0), "lever": (2, None, 1.5)}
+LEVER_MM = 3.0
+LONG = ("5x6x600", "6x5x515", "3x4x1024", "65535x2x3", "3x65535x2", "2x3x65535")  # the shapes "lever" runs on
 # (case, kind, padding, amplitude): every shape at the small amplitude; at the large one every shape but 2x2x2
-# (there every sample leaves the volume, W = 0 and there is no scale to gate against)
-VALUE_CASES = [(c, k, p, a) for a in AMPLITUDES for c in CASES for k in KINDS for p in PADDINGS
-               if not (c == "2x2x2" and a == "large")]
+# (there every sample leaves the volume, W = 0 and there is no scale to gate against); the long shapes at "lever"
+VALUE_CASES = [(c, k, p, a) for a in ("small", "large") for c in CASES for k in KINDS for p in PADDINGS
+               if not (c == "2x2x2" and a == "large")] + \
+    [(c, k, p, "lever") for c in LONG for k in KINDS for p in PADDINGS]
 SEED = 2100  # (with it every large scene has more than 0.2 of its samples outside the volume)
 KW = dict(parameterization="euler_angles", convention="ZXY")
 
@@ -71,6 +81,8 @@ def scene(case, kind, amplitude):
     bounds, their lattice weights, a uniform upstream gradient.  Shared by every test of the case; never modified."""
     dims, grid = CASES[case]
     K, rotation, translation = AMPLITUDES[amplitude]
+    if rotation is None:
+        rotation = LEVER_MM / (0.5 * sum((h * (D - 1)) ** 2 for h, D in zip(PITCH, dims)) ** 0.5)
     g = torch.Generator().manual_seed(SEED + 7 * len(case) + K + (kind == "phantom"))
     V = torch.rand(*dims, generator=g) if kind == "noise" else phantom_volume(dims, seed=3).contiguous()
     theta = torch.cat((bounded(g, K, rotation), bounded(g, K, translation)), dim=1)
@@ -227,7 +239,7 @@ def check_exact_translation(device):
 
 def check_reproducible(device, ops):
     """Forward and the twist gradient, each run twice, agree bit for bit (several pieces per cell, with tails)."""
-    for case in ("40x36x130", "23x30x37"):
+    for case in ("40x36x130", "23x30x37", "5x6x600", "3x4x1024"):
         V, theta, weights, gW = (t.to(device) for t in scene(case, "noise", "large"))
         Xi = twist_lattice(theta, weights)
         for padding in PADDINGS:

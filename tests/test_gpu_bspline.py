@@ -4,8 +4,10 @@ import pytest
 import torch
 
 import bspline_cases
+import large_deformation as large
 from diffdrr_amd import DRR, FreeFormDeformation, ops, warp_reference, warp_volume
 from diffdrr_amd.data import make_subject, phantom_volume
+from diffdrr_amd.deformation import dense_field
 
 pytestmark = pytest.mark.gpu
 BASIS = bspline_cases.BASIS
@@ -71,3 +73,30 @@ def test_cpu_tensors_are_rejected(gpu):
         ops.bspline_forward(V, U.to(gpu))
     with pytest.raises(ValueError, match="GPU only"):
         warp_volume(V, U, basis=BASIS)
+
+
+LARGE_SEED = 1  # (the first seed from 1 that keeps large_deformation.FACE_MARGIN)
+
+
+@pytest.mark.parametrize("padding", bspline_cases.PADDINGS)
+def test_volume_past_2_to_the_30_voxels(gpu, padding):
+    """W, gV and gU of a (1040, 1024, 1024) volume on four windows (tests/large_deformation.py): byte offsets
+    past 2 GiB and 4 GiB.  gU is gated per component on bspline_cases' scale, summed over the windows."""
+    U = large.lattice(LARGE_SEED, 5.0)
+
+    def gate_gU(name, names, got, ref64, ref32, held):
+        spread = sum(bspline_cases.coefficient_gradient_spread(part, U, gW, padding, box, (large.SHAPE, reach))
+                     for box, reach, part, gW in held)
+        own = [float((ref32[0][a].double() - ref64[0][a]).abs().max()) for a in range(3)]
+        bspline_cases.gate_gU(name, got[0], ref64[0], own, [float(spread[a].max()) for a in range(3)])
+
+    large.check(f"bspline {padding}", gpu, LARGE_SEED, (U,), ("gU",),
+                kernel=lambda V, U: warp_volume(V, U, padding, BASIS),
+                definition=lambda V, U, box, part: warp_reference(V, U, padding, BASIS, box=box, part=part),
+                field=lambda box: dense_field(U.double(), large.SHAPE, BASIS, box=box), lattice_gate=gate_gU)
+
+
+def test_sizes_outside_the_domain_are_refused_before_any_launch(gpu, monkeypatch):
+    U = torch.zeros(3, 2, 2, 2, device=gpu)
+    large.check_domain_errors(monkeypatch, ops, "_launch_bspline", lambda V: ops.bspline_forward(V, U),
+                              lambda shape: ops._check_bspline("bspline_forward", shape, U, "zeros"), U)

@@ -1,9 +1,12 @@
 """Polyrigid deformation on the MI355X: the checks of tests/test_polyrigid.py through the gfx950 kernels
 (libdiffdrr_polyrigid_hip.so)."""
 import pytest
+import torch
 
+import large_deformation as large
 import polyrigid_cases as cases
-from diffdrr_amd import ops, twist_lattice
+from diffdrr_amd import ops, polyrigid_reference, polyrigid_warp, twist_lattice
+from diffdrr_amd.polyrigid import displacement_field
 
 pytestmark = pytest.mark.gpu
 
@@ -64,3 +67,33 @@ def test_cpu_tensors_are_rejected(gpu):
         ops.polyrigid_forward(V.to(gpu), Xi)
     with pytest.raises(ValueError, match="volume is on cpu.*GPU only"):
         ops.polyrigid_forward(V, Xi.to(gpu))
+
+
+LARGE_SEED = 4  # (the first seed from 1 that keeps large_deformation.FACE_MARGIN)
+
+
+def large_bodies(seed):
+    """Two bodies on large.GRID, |omega| <= 0.003 rad and |v| <= 2 mm: with cases.PITCH the corners of the
+    (1040, 1024, 1024) volume lie 1440 mm from its centre and move by at most 4.3 + 2 mm = 7.9 voxels of 0.8 mm."""
+    g = torch.Generator().manual_seed(seed)
+    theta = torch.cat((cases.bounded(g, 2, 0.003), cases.bounded(g, 2, 2.0)), dim=1)
+    return theta, cases.random_weights(g, 2, large.GRID)
+
+
+@pytest.mark.parametrize("padding", cases.PADDINGS)
+def test_volume_past_2_to_the_30_voxels(gpu, padding):
+    """W, gV, g theta and g weights of a (1040, 1024, 1024) volume on four windows (tests/large_deformation.py):
+    byte offsets past 2 GiB and 4 GiB."""
+    theta, weights = large_bodies(LARGE_SEED)
+    Xi = twist_lattice(theta.double(), weights.double())
+    large.check(f"polyrigid {padding}", gpu, LARGE_SEED, (theta, weights), ("g theta", "g weights"),
+                kernel=lambda V, t, w: polyrigid_warp(V, t, w, cases.PITCH, padding),
+                definition=lambda V, t, w, box, part: polyrigid_reference(V, t, w, cases.PITCH, padding, box, part),
+                field=lambda box: displacement_field(Xi, large.SHAPE, cases.PITCH, box))
+
+
+def test_sizes_outside_the_domain_are_refused_before_any_launch(gpu, monkeypatch):
+    Xi = torch.zeros(6, 2, 2, 2, device=gpu)
+    large.check_domain_errors(
+        monkeypatch, ops, "_launch_polyrigid", lambda V: ops.polyrigid_forward(V, Xi),
+        lambda shape: ops._check_polyrigid("polyrigid_forward", shape, Xi, (1.0, 1.0, 1.0), "zeros"), Xi)

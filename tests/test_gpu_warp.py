@@ -3,8 +3,10 @@
 import pytest
 import torch
 
+import large_deformation as large
 import warp_cases
-from diffdrr_amd import ops
+from diffdrr_amd import ops, warp_reference, warp_volume
+from diffdrr_amd.deformation import dense_field, sample_displaced
 
 pytestmark = pytest.mark.gpu
 
@@ -55,3 +57,25 @@ def test_cpu_tensors_are_rejected(gpu):
         ops.warp_forward(V.to(gpu), U)
     with pytest.raises(ValueError, match="volume is on cpu.*GPU only"):
         ops.warp_forward(V, U.to(gpu))
+
+
+LARGE_SEED = 1  # (the first seed from 1 that keeps large_deformation.FACE_MARGIN)
+
+
+@pytest.mark.parametrize("padding", warp_cases.PADDINGS)
+def test_volume_past_2_to_the_30_voxels(gpu, padding):
+    """W, gV and gU of a (1040, 1024, 1024) volume on four windows (tests/large_deformation.py): byte offsets
+    past 2 GiB and 4 GiB.  The float32 yardstick is warp_cases.reference's."""
+    U = large.lattice(LARGE_SEED, 3.0)
+    large.check(f"warp {padding}", gpu, LARGE_SEED, (U,), ("gU",),
+                kernel=lambda V, U: warp_volume(V, U, padding),
+                definition=lambda V, U, box, part: warp_reference(V, U, padding, box=box, part=part),
+                float32_definition=lambda V, U, box, part: sample_displaced(
+                    V, dense_field(U, large.SHAPE, box=box), padding, box, part),
+                field=lambda box: dense_field(U.double(), large.SHAPE, box=box))
+
+
+def test_sizes_outside_the_domain_are_refused_before_any_launch(gpu, monkeypatch):
+    U = torch.zeros(3, 2, 2, 2, device=gpu)
+    large.check_domain_errors(monkeypatch, ops, "_launch_warp", lambda V: ops.warp_forward(V, U),
+                              lambda shape: ops._check_warp("warp_forward", shape, U, "zeros"), U)

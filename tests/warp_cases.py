@@ -1,9 +1,11 @@
 """What tests/test_warp.py (host emulation) and tests/test_gpu_warp.py (MI355X) share: the host build of
 csrc/warp_core.h, the scenes, the float64 yardsticks and the checks themselves, written once for either device.
 
-The gate follows the project's rule: ``warp_reference`` evaluated in float32 on the CPU has an error of its own
+The gate follows the project's rule: the definition evaluated in float32 on the CPU has an error of its own
 against ``warp_reference`` in float64; the kernels may be off by at most twice that, plus a floor of 1e-6 of the
-compared tensor's scale (max |reference|)."""
+compared tensor's scale (max |reference|).  The float32 side is ``sample_displaced(V, dense_field(U))``, the same
+function with floor and fraction formed from u, as the kernels form them: ``warp_reference`` rounds p = x + u
+itself, which costs 2^-8 voxel at x near 65535 -- in float32 a yardstick thousands of times the kernels' error."""
 import copy
 import functools
 import os
@@ -14,7 +16,7 @@ import torch
 from conftest import ROOT
 from diffdrr_amd import DRR, FreeFormDeformation, _lib, warp_reference, warp_volume
 from diffdrr_amd.data import make_subject, phantom_volume
-from diffdrr_amd.deformation import dense_field, sample_coordinates
+from diffdrr_amd.deformation import dense_field, sample_coordinates, sample_displaced
 
 EMU_SRC = os.path.join(ROOT, "tests", "emu", "warp_emu.cpp")
 EMU_SO = os.path.join(ROOT, "tests", "emu", "_build", "libwarp_emu.so")
@@ -26,6 +28,13 @@ CASES = {
     "9x10x133": ((9, 10, 133), (2, 3, 17)),      # node spacing 8.25 voxels: cells of unequal extents
     "2x2x2": ((2, 2, 2), (2, 2, 2)),             # the smallest possible case
     "40x36x130": ((40, 36, 130), (3, 3, 5)),     # several workgroups per cell, with tails
+    # rows of several 256-voxel z chunks (the B-spline kernels' unit), one node per voxel, the 65535 limit
+    "5x6x600": ((5, 6, 600), (3, 4, 7)),         # three z chunks, chunk ends inside cells, nothing a multiple of 4
+    "6x5x515": ((6, 5, 515), (2, 5, 515)),       # a node per voxel on y and z, a last chunk of 3 voxels
+    "3x4x1024": ((3, 4, 1024), (3, 2, 33)),      # Dz a multiple of 4 and of 256: 16-byte stores, exact chunk ends
+    "65535x2x3": ((65535, 2, 3), (9, 2, 2)),     # the limit on x: the longest chains of the lattice gradients
+    "3x65535x2": ((3, 65535, 2), (2, 65535, 2)),  # the limit on y with a node per voxel
+    "2x3x65535": ((2, 3, 65535), (2, 3, 700)),   # the limit on z: 256 chunks per row
 }
 KINDS = ("noise", "phantom")
 PADDINGS = ("zeros", "border")
@@ -80,9 +89,11 @@ def near_face_fraction(U64, dims):
 
 
 def reference(V, U, gW, padding, dtype):
-    """(W, gV, gU) of ``warp_reference`` in `dtype` on the CPU, as float64 tensors."""
+    """(W, gV, gU) of the definition in `dtype` on the CPU, as float64 tensors: ``warp_reference`` in float64,
+    ``sample_displaced(V, dense_field(U))`` in float32 (the module's docstring says why)."""
     V, U = V.to(dtype).requires_grad_(), U.to(dtype).requires_grad_()
-    W = warp_reference(V, U, padding)
+    W = warp_reference(V, U, padding) if dtype == torch.float64 else \
+        sample_displaced(V, dense_field(U, V.shape), padding)
     gV, gU = torch.autograd.grad(W, (V, U), gW.to(dtype))
     return W.detach().double(), gV.double(), gU.double()
 
@@ -161,8 +172,9 @@ def check_identity(case, kind, padding, device):
 
 
 def check_reproducible(device, ops):
-    """Forward and the lattice gradient, each run twice, agree bit for bit (several workgroups per cell)."""
-    for case in ("40x36x130", "23x30x37"):
+    """Forward and the lattice gradient, each run twice, agree bit for bit (several workgroups per cell; rows of
+    several z chunks, with and without 16-byte stores)."""
+    for case in ("40x36x130", "23x30x37", "5x6x600", "3x4x1024"):
         V, U, gW = (t.to(device) for t in scene(case, "noise", 2.5))
         for padding in PADDINGS:
             assert torch.equal(ops.warp_forward(V, U, padding), ops.warp_forward(V, U, padding))
