@@ -8,7 +8,11 @@ the reference's own module API (``DRR``, ``Detector``, ``RigidTransform`` /
 __version__ = "0.1.0"
 
 from .analytic import backproject, fbp_filter, fdk, ramp_taps  # noqa: F401
-from .deformation import FreeFormDeformation, bspline_weights, dense_field, warp_reference, warp_volume  # noqa: F401
+from .deformation import (  # noqa: F401
+    FreeFormDeformation, JacobianStatistics, bspline_derivative_weights, bspline_weights, dense_field, field_jacobian,
+    jacobian_determinant, jacobian_reference, jacobian_statistics, volume_penalty, volume_penalty_reference,
+    warp_reference, warp_volume,
+)
 from .detector import Detector  # noqa: F401
 from .drr import DRR  # noqa: F401
 from .metrics import (  # noqa: F401

@@ -33,6 +33,7 @@ LM_ABI_VERSION = 1
 WARP_ABI_VERSION = 1
 BSPLINE_ABI_VERSION = 1
 POLYRIGID_ABI_VERSION = 1
+JACOBIAN_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -397,3 +398,35 @@ def get_polyrigid_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _polyrigid_lib = polyrigid_library(POLYRIGID_LIB_PATH)
     return _polyrigid_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_jacobian_hip.so
+# Jacobian determinant of a lattice deformation, folding statistics, volume penalty and their lattice gradient
+# (C ABI: include/diffdrr_jacobian_hip.h)
+JACOBIAN_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_jacobian_hip.so")
+JACOBIAN_HEADER = Header.read("diffdrr_jacobian_hip.h", "ddrr_jacobian", JACOBIAN_ABI_VERSION)
+_JACOBIAN_SIGNATURES, _JACOBIAN_RESTYPES, JACOBIAN_EXPORTS = JACOBIAN_HEADER.tables()
+JACOBIAN_BASIS_LINEAR, JACOBIAN_BASIS_BSPLINE, JACOBIAN_MAX_DIM, JACOBIAN_PARTIAL_BYTES = \
+    JACOBIAN_HEADER.constants("BASIS_LINEAR", "BASIS_BSPLINE", "MAX_DIM", "PARTIAL_BYTES")
+
+
+def jacobian_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_jacobian_hip.h."""
+    return DdrrLibrary(path, JACOBIAN_HEADER)
+
+
+_jacobian_lib: DdrrLibrary | None = None
+
+
+def get_jacobian_lib() -> DdrrLibrary:
+    """The Jacobian determinant library, loaded on first use.  Raises if it has not been built."""
+    global _jacobian_lib
+    if _jacobian_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(JACOBIAN_LIB_PATH):
+            raise RuntimeError(
+                f"{JACOBIAN_LIB_PATH} is missing: the Jacobian determinant kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _jacobian_lib = jacobian_library(JACOBIAN_LIB_PATH)
+    return _jacobian_lib

@@ -10,8 +10,17 @@ field from 4 x 4 x 4 coefficients per voxel, border coefficients edge-replicated
 not that node's coefficient.  ``basis="linear"``, the default, is the trilinear field.
 
 :func:`warp_reference` is the definition in pure torch, for any dtype: the float64 yardstick of the tests.
+
+Whether the map ``x -> x + u(x)`` is still a deformation is read off its Jacobian determinant
+(``csrc/jacobian.hip``, ``include/diffdrr_jacobian_hip.h``): :func:`jacobian_determinant` (the map, differentiable),
+:func:`jacobian_statistics` (folded voxels, extremes) and :func:`volume_penalty` (the fused regulariser on
+``ln det``), with :func:`field_jacobian`, :func:`jacobian_reference` and :func:`volume_penalty_reference` as their
+definitions in torch.
 """
 from __future__ import annotations
+
+import math
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -51,6 +60,11 @@ def bspline_weights(t: torch.Tensor):
     return ((1 - t) ** 3 / 6, (3 * t ** 3 - 6 * t ** 2 + 4) / 6, (-3 * t ** 3 + 3 * t ** 2 + 3 * t + 1) / 6, t ** 3 / 6)
 
 
+def bspline_derivative_weights(t: torch.Tensor):
+    """The derivatives in ``t`` of the four :func:`bspline_weights` (include/diffdrr_jacobian_hip.h)."""
+    return (-(1 - t) ** 2 / 2, (3 * t ** 2 - 4 * t) / 2, (-3 * t ** 2 + 2 * t + 1) / 2, t ** 2 / 2)
+
+
 def dense_field(displacement: torch.Tensor, shape, basis: str = "linear", box=None) -> torch.Tensor:
     """u (3, Dx, Dy, Dz): the lattice ``displacement`` (3, Gx, Gy, Gz) evaluated at every voxel, node i of axis a
     at voxel coordinate i (D_a - 1) / (G_a - 1): interpolated trilinearly (``basis="linear"``), or the cubic
@@ -69,6 +83,66 @@ def dense_field(displacement: torch.Tensor, shape, basis: str = "linear", box=No
         else:
             u = sum(w * u.index_select(axis + 1, (c - 1 + k).clamp(0, G - 1)) for k, w in enumerate(bspline_weights(t)))
     return u
+
+
+def field_jacobian(displacement: torch.Tensor, shape, basis: str = "linear", box=None) -> torch.Tensor:
+    """du_a / dx_b, (3, 3, Dx, Dy, Dz), of :func:`dense_field` at every voxel: the analytic derivative of the
+    basis in the cell the voxel is assigned to (include/diffdrr_jacobian_hip.h) -- axis b takes derivative weights
+    times (G_b - 1) / (D_b - 1), the other two axes the field's own weights.  For ``basis="linear"`` it is
+    piecewise constant along b and one-sided at node planes (a voxel on a node gets its own cell's slope); for
+    ``basis="bspline"`` it is continuous.  Any dtype: in float64, the yardstick of the kernels."""
+    _check_basis(basis)
+    columns = []
+    for b in range(3):
+        u = displacement
+        for axis, D in enumerate(shape):
+            G = u.shape[axis + 1]
+            c, t = _cells(int(D), G, u.device, u.dtype, _span(D, box, axis))
+            t = t.reshape([-1 if d == axis + 1 else 1 for d in range(4)])
+            scale = (G - 1) / (int(D) - 1) if axis == b else 1.0
+            if basis == "linear":
+                lo, hi = u.index_select(axis + 1, c), u.index_select(axis + 1, c + 1)
+                u = (hi - lo) * scale if axis == b else (1 - t) * lo + t * hi
+            else:
+                ws = bspline_derivative_weights(t) if axis == b else bspline_weights(t)
+                u = sum(w * u.index_select(axis + 1, (c - 1 + k).clamp(0, G - 1)) for k, w in enumerate(ws)) * scale
+        columns.append(u)
+    return torch.stack(columns, dim=1)
+
+
+def _determinant(J: torch.Tensor) -> torch.Tensor:
+    """det of (3, 3, ...) by cofactor expansion along the first row."""
+    return (J[0, 0] * (J[1, 1] * J[2, 2] - J[1, 2] * J[2, 1]) + J[0, 1] * (J[1, 2] * J[2, 0] - J[1, 0] * J[2, 2])
+            + J[0, 2] * (J[1, 0] * J[2, 1] - J[1, 1] * J[2, 0]))
+
+
+def jacobian_reference(displacement: torch.Tensor, shape, basis: str = "linear") -> torch.Tensor:
+    """The definition of :func:`jacobian_determinant` in torch: det(I + du/dx) of :func:`field_jacobian`,
+    (Dx, Dy, Dz), in the dtype of the lattice; autograd gives the lattice gradient."""
+    J = field_jacobian(displacement, shape, basis)
+    eye = torch.eye(3, dtype=J.dtype, device=J.device).reshape(3, 3, 1, 1, 1)
+    return _determinant(J + eye)
+
+
+def _check_eps(eps):
+    if not 0.0 < float(eps) <= 1.0:
+        raise ValueError(f"eps must be in (0, 1], got {eps!r}")
+
+
+def volume_penalty_of(det: torch.Tensor, eps: float = 0.1) -> torch.Tensor:
+    """psi of a determinant map, elementwise: ln^2 d for d >= eps, its C^2 quadratic continuation below
+    (include/diffdrr_jacobian_hip.h)."""
+    _check_eps(eps)
+    le = math.log(eps)
+    x = det - eps
+    below = le * le + (2 * le / eps) * x + ((1 - le) / eps ** 2) * x * x
+    return torch.where(det >= eps, det.clamp(min=eps).log() ** 2, below)
+
+
+def volume_penalty_reference(displacement: torch.Tensor, shape, basis: str = "linear", eps: float = 0.1):
+    """The definition of :func:`volume_penalty` in torch: the mean of psi(det) over the voxels (Rohlfing et al.
+    2003, with a quadratic continuation below ``eps`` so that a folded start has a finite gradient)."""
+    return volume_penalty_of(jacobian_reference(displacement, shape, basis), eps).mean()
 
 
 def sample_coordinates(displacement: torch.Tensor, shape, basis: str = "linear", box=None) -> torch.Tensor:
@@ -192,6 +266,69 @@ class _BsplineFn(torch.autograd.Function):
         return g_volume, g_disp, None
 
 
+class _JacobianFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, displacement, shape, basis):
+        ctx.shape, ctx.basis = shape, basis
+        ctx.save_for_backward(displacement)
+        return ops.jacobian_determinant(displacement, shape, basis)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        displacement, = ctx.saved_tensors
+        return ops.jacobian_backward(displacement, ctx.shape, grad_out.contiguous(), ctx.basis), None, None
+
+
+class _VolumePenaltyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, displacement, shape, basis, eps):
+        ctx.shape, ctx.basis, ctx.eps = shape, basis, eps
+        ctx.save_for_backward(displacement)
+        return ops.jacobian_penalty(displacement, shape, basis, eps)[0].to(torch.float32).reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        displacement, = ctx.saved_tensors
+        return grad_out * ops.jacobian_backward(displacement, ctx.shape, None, ctx.basis, ctx.eps), None, None, None
+
+
+class JacobianStatistics(NamedTuple):
+    """Where the map x -> x + u(x) folds: device tensors, no host synchronisation."""
+    folded: torch.Tensor    # int64 scalar: the number of voxels with det <= 0
+    minimum: torch.Tensor   # float32 scalar: min det
+    maximum: torch.Tensor   # float32 scalar: max det
+
+
+def jacobian_determinant(displacement: torch.Tensor, shape, basis: str = "linear") -> torch.Tensor:
+    """det(I + du/dx) at every voxel of a volume of ``shape`` (Dx, Dy, Dz), for the lattice ``displacement``
+    (3, Gx, Gy, Gz) in voxels of each axis, float32, contiguous and on the GPU, 2 <= G_a <= D_a: the local volume
+    change of the map x -> x + u(x); <= 0 where it folds.  ``u`` as in :func:`warp_volume`; the derivative is the
+    analytic one of the voxel's cell (:func:`field_jacobian`), so for ``basis="linear"`` it is piecewise and
+    one-sided at node planes.  Differentiable in ``displacement`` (no atomics: bitwise reproducible).  The
+    determinant does not depend on the voxel pitch.  Anything outside the domain raises ValueError naming the
+    condition."""
+    dims, _, _ = ops._check_jacobian("jacobian_determinant", shape, displacement, basis)
+    return _JacobianFn.apply(displacement, dims, basis)
+
+
+def jacobian_statistics(displacement: torch.Tensor, shape, basis: str = "linear") -> JacobianStatistics:
+    """(folded, minimum, maximum) of :func:`jacobian_determinant` without the map in memory and without a host
+    synchronisation: the number of voxels with det <= 0 and the extremes, as device scalars."""
+    _, folded, rng = ops.jacobian_penalty(displacement.detach(), shape, basis, 1.0)
+    return JacobianStatistics(folded[0], rng[0], rng[1])
+
+
+def volume_penalty(displacement: torch.Tensor, shape, basis: str = "linear", eps: float = 0.1) -> torch.Tensor:
+    """The volume-preservation penalty (1 / N) sum_x psi(det J(x)), psi = ln^2 above ``eps`` and its C^2 quadratic
+    continuation below (finite, with a finite gradient, for folded voxels), 0 < eps <= 1: a differentiable
+    float32 scalar, fused -- neither the derivative field nor the determinant map is in memory, forward or
+    backward.  The arguments are those of :func:`jacobian_determinant`."""
+    dims, _, _ = ops._check_jacobian("volume_penalty", shape, displacement, basis, eps)
+    return _VolumePenaltyFn.apply(displacement, dims, basis, float(eps))
+
+
 def warp_volume(volume: torch.Tensor, displacement: torch.Tensor, padding: str = "zeros",
                 basis: str = "linear") -> torch.Tensor:
     """``W[x] = V(x + u(x))``: ``volume`` (Dx, Dy, Dz) and the lattice ``displacement`` (3, Gx, Gy, Gz), in
@@ -243,7 +380,7 @@ class FreeFormDeformation(nn.Module):
 
     def warped(self) -> torch.Tensor:
         """The deformed volume (the shape of ``drr``'s)."""
-        return warp_volume(self.drr.density, (self.displacement / self.pitch).contiguous(), self.padding, self.basis)
+        return warp_volume(self.drr.density, self._voxel_lattice(), self.padding, self.basis)
 
     def forward(self, *pose_args, **kwargs):
         buffers = self.drr._buffers
@@ -253,6 +390,29 @@ class FreeFormDeformation(nn.Module):
             return self.drr(*pose_args, **kwargs)
         finally:
             buffers["density"] = theirs
+
+    def _voxel_lattice(self) -> torch.Tensor:
+        return (self.displacement / self.pitch).contiguous()
+
+    def jacobian_determinant(self) -> torch.Tensor:
+        """det(I + du/dx) at every voxel of the volume (:func:`jacobian_determinant` of ``displacement / pitch``,
+        as :meth:`warped` reads it), differentiable in ``displacement``.  The determinant is independent of the
+        pitch: in millimetres J is S J S^-1.  For ``basis="linear"`` it is piecewise constant along each axis and
+        one-sided at node planes."""
+        return jacobian_determinant(self._voxel_lattice(), tuple(self.drr.density.shape), self.basis)
+
+    def folding(self) -> JacobianStatistics:
+        """(folded, minimum, maximum): the number of voxels where the deformation folds (det <= 0) and the
+        extremes of the determinant, as device scalars without a host synchronisation and without the map in
+        memory.  Independent of the pitch; for ``basis="linear"`` piecewise and one-sided at node planes."""
+        return jacobian_statistics(self._voxel_lattice(), tuple(self.drr.density.shape), self.basis)
+
+    def volume_penalty(self, eps: float = 0.1) -> torch.Tensor:
+        """The volume-preservation regulariser (:func:`volume_penalty`): the mean over the voxels of ln^2 det,
+        continued quadratically below ``eps`` so that a folded lattice is pushed back.  Differentiable in
+        ``displacement`` (millimetres); independent of the pitch; for ``basis="linear"`` the determinant is
+        piecewise and one-sided at node planes."""
+        return volume_penalty(self._voxel_lattice(), tuple(self.drr.density.shape), self.basis, eps)
 
     def smoothness(self) -> torch.Tensor:
         """Mean squared first difference of the lattice (mm^2), over the three lattice axes."""

@@ -1884,6 +1884,81 @@ def bspline_backward_volume(displacement, grad_out, padding="zeros"):
     return out
 
 
+# ------------------------------------------------- Jacobian determinant (libdiffdrr_jacobian_hip.so)
+_JACOBIAN_BASIS = {"linear": _lib.JACOBIAN_BASIS_LINEAR, "bspline": _lib.JACOBIAN_BASIS_BSPLINE}
+
+
+def _launch_jacobian(name, device, *args):
+    """:func:`_launch` through the Jacobian determinant library."""
+    _launch_on(_lib.get_jacobian_lib(), name, device, args)
+
+
+def _query_jacobian(name, *args):
+    return _lib.get_jacobian_lib().query(name, *args)
+
+
+def _check_jacobian(name, shape, displacement, basis, eps=None, **volumes):
+    """The domain of include/diffdrr_jacobian_hip.h -- that of :func:`_check_warp`, the basis and ``eps`` in
+    (0, 1], each condition by name -> (dims, grid, basis code)."""
+    if basis not in _JACOBIAN_BASIS:
+        raise ValueError(f"{name}: basis must be 'linear' or 'bspline', not {basis!r}")
+    if eps is not None and not 0.0 < float(eps) <= 1.0:
+        raise ValueError(f"{name}: eps must be in (0, 1], got {eps!r}")
+    dims, grid, _ = _check_warp(name, shape, displacement, "zeros", **volumes)
+    return dims, grid, _JACOBIAN_BASIS[basis]
+
+
+def _jacobian_workspace(name, dims, grid, code, device):
+    n = int(_query_jacobian("ddrr_jacobian_workspace_bytes", *dims, *grid, code))
+    if n < 0:
+        raise ValueError(f"{name}: a lattice of {grid} on a volume of {dims} needs more than 2^31 - 1 (cell, piece) "
+                         "workgroups")
+    return torch.empty((n + 7) // 8, dtype=torch.float64, device=device), n
+
+
+def jacobian_determinant(displacement, shape, basis="linear"):
+    """det(I + du/dx) at every voxel of a volume of ``shape`` for the lattice ``displacement`` (3, Gx, Gy, Gz) in
+    voxels, and its statistics (ddrr_jacobian_determinant) -> (map of ``shape``, folded: one int64 on the device,
+    range: (min, max) float32 on the device).  No host synchronisation."""
+    dims, grid, code = _check_jacobian("jacobian_determinant", shape, displacement, basis)
+    dev = displacement.device
+    ws, n = _jacobian_workspace("jacobian_determinant", dims, grid, code, dev)
+    out = torch.empty(dims, dtype=torch.float32, device=dev)
+    folded = torch.empty(1, dtype=torch.int64, device=dev)
+    rng = torch.empty(2, dtype=torch.float32, device=dev)
+    _launch_jacobian("ddrr_jacobian_determinant", dev, displacement.data_ptr(), *grid, *dims, code, out.data_ptr(),
+                     ws.data_ptr(), n, folded.data_ptr(), rng.data_ptr())
+    return out, folded, rng
+
+
+def jacobian_penalty(displacement, shape, basis="linear", eps=0.1):
+    """The mean of psi(det) over the voxels and the statistics, with no map in memory (ddrr_jacobian_penalty)
+    -> (penalty: one float64 on the device, folded, range) as :func:`jacobian_determinant`."""
+    dims, grid, code = _check_jacobian("jacobian_penalty", shape, displacement, basis, eps)
+    dev = displacement.device
+    ws, n = _jacobian_workspace("jacobian_penalty", dims, grid, code, dev)
+    penalty = torch.empty(1, dtype=torch.float64, device=dev)
+    folded = torch.empty(1, dtype=torch.int64, device=dev)
+    rng = torch.empty(2, dtype=torch.float32, device=dev)
+    _launch_jacobian("ddrr_jacobian_penalty", dev, displacement.data_ptr(), *grid, *dims, code, float(eps),
+                     ws.data_ptr(), n, penalty.data_ptr(), folded.data_ptr(), rng.data_ptr())
+    return penalty, folded, rng
+
+
+def jacobian_backward(displacement, shape, grad_out=None, basis="linear", eps=0.1):
+    """The lattice gradient of the determinant map for the upstream ``grad_out`` (``shape``), or of the penalty
+    (psi'(det) / N formed in the kernel) when ``grad_out`` is None (ddrr_jacobian_backward: no atomics, bitwise
+    reproducible) -> (3, Gx, Gy, Gz)."""
+    volumes = {} if grad_out is None else {"grad_out": grad_out}
+    dims, grid, code = _check_jacobian("jacobian_backward", shape, displacement, basis, eps, **volumes)
+    dev = displacement.device
+    ws, n = _jacobian_workspace("jacobian_backward", dims, grid, code, dev)
+    out = torch.empty_like(displacement)
+    _launch_jacobian("ddrr_jacobian_backward", dev, displacement.data_ptr(), *grid, *dims, code, _ptr(grad_out),
+                     float(eps), ws.data_ptr(), n, out.data_ptr())
+    return out
+
+
 # ------------------------------------------------- polyrigid deformation (libdiffdrr_polyrigid_hip.so)
 _POLYRIGID_PADDING = {"zeros": _lib.POLYRIGID_PADDING_ZEROS, "border": _lib.POLYRIGID_PADDING_BORDER}
 
