@@ -976,7 +976,12 @@ __global__ __launch_bounds__(kBlock) void volgrad_prepare_kernel(
             const float side = extent * reach / (sqrtf(rho2) * e_min) + 2.f;
             R = side * side;
         }
-        atomicAdd(reinterpret_cast<float *>(work) + 2, R);
+        // Whole numbers: the poses' workgroups arrive in any order, and a sum of integer-valued floats is
+        // exact (so the same in every order) as long as it is below 2^24 -- the fixed-point path needs
+        // n_sum <= 16384, and a sum that has passed that stays above it.  With R itself the last bit of
+        // n_sum, and with it the scale of the accumulator and the rounding of every voxel, depended on
+        // the order: the one thing that kept two launches of the same gradient from agreeing bit for bit.
+        atomicAdd(reinterpret_cast<float *>(work) + 2, ceilf(R));
     }
 }
 

@@ -346,6 +346,24 @@ def test_reconstruction_first_three_steps_agree_voxelwise(end_to_end):
     assert diff <= 1e-5
 
 
+def test_volume_gradient_of_the_scene_is_bitwise_reproducible(gpu):
+    """What the three-step comparison above rests on: the two routes get the same volume gradient from the same
+    volume.  The brick kernels accumulate it in fixed point (integer sums: any order), with a scale formed from a
+    bound summed over the poses -- in whole numbers, so that this sum does not depend on the order in which the
+    poses' workgroups arrive either (csrc/bricks.hip volgrad_prepare_kernel).  One brick: every ray's forward
+    value is a single contribution."""
+    truth, geo, kw, rot, xyz, measured, blank = _scene(gpu)
+    recon = Reconstruction(DRR(blank, **geo), init=truth * 0.5).to(gpu)
+    grads = []
+    for _ in range(6):
+        recon.density.grad = None
+        torch.nn.functional.mse_loss(recon(rot, xyz, **kw), measured).backward()
+        grads.append(recon.density.grad.clone())
+    assert float(grads[0].abs().max()) > 0
+    for g in grads[1:]:
+        assert torch.equal(g, grads[0])
+
+
 def test_reconstruction_with_the_trilinear_renderer_reduces_the_loss(gpu):
     truth, geo, kw, rot, xyz, measured, blank = _scene(gpu, renderer="trilinear")
     recon = Reconstruction(DRR(blank, **geo), lower=0.0).to(gpu)
