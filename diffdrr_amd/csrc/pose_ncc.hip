@@ -803,7 +803,17 @@ __global__ __launch_bounds__(kBlurBlock) void blur_sobel_bwd_kernel(
 //   step += 1;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
 //   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)        (maximize: g = -g)
 // One workgroup: the counters are read by every thread before any is written.
+// The bias corrections are worked out in double, as torch works them out on the host: 1 - beta^step in float
+// loses what beta^step rounds away -- 2^-24 against 1 - beta2^step ~ 1e-3 step, 1e-5 of the step size in the
+// first steps, thirty times what torch's float32 Adam is off by.  beta^step for the whole number a step
+// counter holds, by squaring: a few dozen double multiplications, less than the powf they replace.
 constexpr int kAdamBlock = 256;
+__device__ __forceinline__ double pow_whole(double b, float n) {
+    double r = 1.0;
+    for (unsigned k = (unsigned)n; k; k >>= 1, b *= b)
+        if (k & 1u) r *= b;
+    return r;
+}
 __global__ __launch_bounds__(kAdamBlock) void pose_adam_kernel(
     float *__restrict__ rot, float *__restrict__ xyz, const float *__restrict__ g_rot,
     const float *__restrict__ g_xyz, float *__restrict__ m_rot, float *__restrict__ v_rot,
@@ -815,8 +825,8 @@ __global__ __launch_bounds__(kAdamBlock) void pose_adam_kernel(
     float ss[2], rb2[2];  // lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step)
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        ss[k] = (k ? lr_xyz : lr_rot) / (1.f - powf(beta1, steps[k]));
-        rb2[k] = 1.f / sqrtf(1.f - powf(beta2, steps[k]));
+        ss[k] = (float)((double)(k ? lr_xyz : lr_rot) / (1.0 - pow_whole((double)beta1, steps[k])));
+        rb2[k] = (float)(1.0 / sqrt(1.0 - pow_whole((double)beta2, steps[k])));
     }
     const int n = 3 * B;
     for (int i = threadIdx.x; i < 2 * n; i += kAdamBlock) {

@@ -716,6 +716,20 @@ def siddon_backward_pose(aux, grad_out, source, target, img, Mw, Ainv, P, *, eps
 _ncc_ws = {}  # (device, stream, B) -> workspace of ddrr_siddon_ncc_* (zero between calls)
 
 
+def _blocked_record_only(name, aux, B, N):
+    """The fused step's entries read the blocked record alone (no layout argument in their C ABI): any other
+    record, or any other shape, would be misread silently."""
+    if _aux_layout(aux, B, N) != _lib.AUX_BLOCKED:
+        raise ValueError(f"{name} reads the blocked record (ceil(B N / 16), 80) of siddon_forward_bricks only: "
+                         f"aux has shape {tuple(aux.shape)}")
+
+
+def _fixed_rows(name, x1, B, N):
+    if x1.dim() != 2 or x1.shape[1] != N or x1.shape[0] not in (1, B):
+        raise ValueError(f"{name}: x1 has shape {tuple(x1.shape)}: ({B}, {N}), or (1, {N}) for one image shared "
+                         f"by the batch, expected")
+
+
 def siddon_ncc_workspace(B, device):
     """The caller-owned accumulators / tickets of :func:`siddon_ncc_forward` and
     :func:`siddon_ncc_backward_pose`: zero when first handed over, left zero by every call, so one
@@ -762,6 +776,8 @@ def siddon_ncc_forward(aux, img, x1, eps, *, want_image=False, want_sum=False):
     -> (ncc (B), stats (B,5), image (B,N) | None[, sum of the B values (0-dim), with ``want_sum``:
     put together by the same launch])"""
     B, N = img.shape
+    _blocked_record_only("siddon_ncc_forward", aux, B, N)
+    _fixed_rows("siddon_ncc_forward", x1, B, N)
     shared = x1.shape[0] == 1 and B != 1
     x1, img = x1.contiguous(), img.contiguous()
     dev = img.device
@@ -801,6 +817,8 @@ def siddon_ncc_backward_pose(aux, img, x1, stats, g_out, source, target, Mw, Ain
     """(g_rot (B,3), g_xyz (B,3)) of sum_b g_out[b] ncc[b]: ncc_backward, siddon_backward_pose and
     pose_euler_backward in one launch."""
     B, N = img.shape
+    _blocked_record_only("siddon_ncc_backward_pose", aux, B, N)
+    _fixed_rows("siddon_ncc_backward_pose", x1, B, N)
     shared = x1.shape[0] == 1 and B != 1
     g_out, g_stride = _batch_grad(g_out, B)
     x1, img, source, target = (t.contiguous() for t in (x1, img, source, target))
@@ -823,6 +841,7 @@ def siddon_backward_pose_euler(aux, grad_out, source, Mw, Ainv, P, rot, xyz, axe
     """(g_rot (B,3), g_xyz (B,3)) of any objective of the image with per-pixel gradient ``grad_out`` (B, N):
     siddon_backward_pose and pose_euler_backward in one launch (the rays as pose_raygen_forward made them)."""
     B, N = grad_out.shape
+    _blocked_record_only("siddon_backward_pose_euler", aux, B, N)
     grad_out, source = grad_out.contiguous(), source.contiguous()
     Mw, Ainv, P, rot, xyz, reorient34 = (t.contiguous() for t in (Mw, Ainv, P, rot, xyz, reorient34))
     dev = grad_out.device

@@ -562,6 +562,8 @@ int ddrr_siddon_backward_pose_euler(const float *aux, const float *grad_out, con
  *   step += 1;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
  *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)      (maximize: g = -g)
  * m_*, v_* (B, 3) and step_* (1 float each) are the optimizer's state, zero before the first step.
+ * The two bias corrections are worked out in double from the float hyper-parameters, as torch works
+ * them out on the host (the step counters hold whole numbers); the rest is float arithmetic.
  * torch's fused Adam takes four launches for the two groups (diffdrr_amd.registration.PoseAdam is
  * the torch.optim.Optimizer over this entry). */
 int ddrr_pose_adam_step(float *rot, float *xyz, const float *g_rot, const float *g_xyz, float *m_rot,

@@ -1608,8 +1608,15 @@ int ddrr_pose_adam_step(float *rot, float *xyz, const float *g_rot, const float 
         const float *gp = k ? g_xyz : g_rot;
         if (B == 0) continue;
         const float step = st[0] + 1.f;
-        const float ss = (k ? lr_xyz : lr_rot) / (1.f - powf(beta1, step));
-        const float rb2 = 1.f / sqrtf(1.f - powf(beta2, step));
+        // (the bias corrections in double, beta^step by squaring: csrc/pose_ncc.hip pow_whole)
+        const auto pow_whole = [](double b, float n) {
+            double r = 1.0;
+            for (unsigned e = (unsigned)n; e; e >>= 1, b *= b)
+                if (e & 1u) r *= b;
+            return r;
+        };
+        const float ss = (float)((double)(k ? lr_xyz : lr_rot) / (1.0 - pow_whole((double)beta1, step)));
+        const float rb2 = (float)(1.0 / sqrt(1.0 - pow_whole((double)beta2, step)));
         for (int j = 0; j < 3 * B; ++j) {
             const float g = maximize ? -gp[j] : gp[j];
             m[j] = fmaf(g - m[j], 1.f - beta1, m[j]);
