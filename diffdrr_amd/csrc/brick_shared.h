@@ -127,33 +127,34 @@ constexpr int BRICK_TRI_CHANNELS_VOLGRAD = 11;  // the same for the marcher (own
 
 
 #if defined(__HIPCC__)
-constexpr int kRor8 = 0x128;  // DPP row_ror:8: lane ^ 8 within each row of 16
+// v_permlane32_swap a, b: the upper 32 lanes of a change places with the lower 32 lanes of b.
+// Afterwards x = a' holds a of lanes 0-31 | b of lanes 0-31, y = b' holds a of lanes 32-63 | b of
+// lanes 32-63 (record_layout.h rec_halfwave_source is the host restatement).
+__device__ __forceinline__ void halfwave_swap(unsigned a, unsigned b, unsigned &x, unsigned &y) {
+    const auto s = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    x = s[0];
+    y = s[1];
+}
 
 // The float backward record of one batch of hits, delivered to the blocked layout of
-// record_layout.h.  Called by ALL lanes of the wave (ok: the lane holds a hit): lane l swaps
-// plane 1 (3) of its hit against plane 0 (2) of lane l ^ 8's, so that the lower half of a
-// 16-lane row carries planes 0 | 1 of its eight hits and the upper half those of its own eight --
-// when the eight are one run of adjacent pixels (they are: length classes are formed per run of 8)
-// each half row is one contiguous 64-byte line: 2 + 2 + 1 atomic instructions as before, but
-// whole lines instead of half lines.  v = {I, S0x, S0z, S1x, S1z}.
+// record_layout.h.  Called by ALL lanes of the wave (ok: the lane holds a hit).  The batch's hits
+// are runs of up to 8 adjacent pixels (length classes are formed per run of 8) that start at ANY
+// lane -- the class queues are compacted -- so the two 32-byte halves of a run's line, planes 0 | 1
+// (2 | 3) of its rays, are brought into ONE instruction by a half-wave exchange: instruction X
+// carries plane 0 (2) of the hits of lanes 0-31 in its lower half and their plane 1 (3) in its
+// upper half, instruction Y the same of the hits of lanes 32-63.  2 + 2 + 1 atomic instructions,
+// and only a run that straddles lanes 31 | 32 has its lines in two of them.
+// v = {I, S0x, S0z, S1x, S1z}.
 __device__ __forceinline__ void deliver_record_blocked(float *__restrict__ aux, bool ok,
                                                        unsigned r, const float v[5]) {
     const unsigned lo = rec_off01(r) | (ok ? 0u : 0x80000000u);  // (sign bit: nothing to add)
-    const int o0 = (int)lo, o1 = (int)(lo + 8u);
-    // X: lanes 0-7 of a row own plane 0 | lanes 8-15 their partner's plane 1
-    // Y: lanes 0-7 their partner's plane 0 | lanes 8-15 own plane 1
-    const int xo = __builtin_amdgcn_update_dpp(o0, o1, kRor8, 0xf, 0xC, false);
-    const int yo = __builtin_amdgcn_update_dpp(o1, o0, kRor8, 0xf, 0x3, false);
-    auto swap_hi = [](float own, float other) {  // lanes 8-15 <- partner's `other`
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-            __builtin_bit_cast(int, own), __builtin_bit_cast(int, other), kRor8, 0xf, 0xC, false));
-    };
-    auto swap_lo = [](float own, float other) {  // lanes 0-7 <- partner's `other`
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-            __builtin_bit_cast(int, own), __builtin_bit_cast(int, other), kRor8, 0xf, 0x3, false));
-    };
-    const float x01 = swap_hi(v[0], v[1]), y01 = swap_lo(v[1], v[0]);
-    const float x23 = swap_hi(v[2], v[3]), y23 = swap_lo(v[3], v[2]);
+    unsigned xu, yu, x01u, y01u, x23u, y23u;
+    halfwave_swap(lo, lo + 8u, xu, yu);
+    halfwave_swap(__float_as_uint(v[0]), __float_as_uint(v[1]), x01u, y01u);
+    halfwave_swap(__float_as_uint(v[2]), __float_as_uint(v[3]), x23u, y23u);
+    const int xo = (int)xu, yo = (int)yu;
+    const float x01 = __uint_as_float(x01u), y01 = __uint_as_float(y01u);
+    const float x23 = __uint_as_float(x23u), y23 = __uint_as_float(y23u);
     if (xo >= 0) {
         unsafeAtomicAdd(aux + xo, x01);
         unsafeAtomicAdd(aux + xo + 16, x23);

@@ -14,9 +14,16 @@
 //     line 3: rays 8-15 plane 2 | rays 8-15 plane 3
 //     line 4: rays 0-15 plane 4
 //
-// and the kernel swaps values between lane l and lane l ^ 8 (one DPP row rotate per plane)
-// so that a 16-lane row of an atomic instruction covers one whole line: 2.5 requests per run
-// of 8 instead of 5.  planes: 0 I, 1 S0x, 2 S0z, 3 S1x, 4 S1z (y follows from the sums).
+// so a run of 8 costs 2.5 requests instead of 5 when both halves of a line, planes 0 | 1 (2 | 3)
+// of its rays, leave in ONE atomic instruction.  The runs of a batch start at any lane (the class
+// queues are compacted; only 47 % of the runs are full), so the delivery (brick_shared.h
+// deliver_record_blocked) exchanges values between the two halves of the wave (rec_halfwave_source
+// below): whatever lane a run starts at, its planes 0 and 1 sit 32 lanes apart in one
+// instruction.  Up to round 6 the exchange was between lane l and lane l ^ 8 of a 16-lane row,
+// which pairs the halves of a line only for runs on 8-lane boundaries: TCC_ATOMIC counted 5.0
+// requests per 8 hits, not the 2.5 claimed here (profiles/r04/traffic.json; the accounting is in
+// DESIGN 3.1, tools/record_requests.py is the model).
+// planes: 0 I, 1 S0x, 2 S0z, 3 S1x, 4 S1z (y follows from the sums).
 #pragma once
 
 #include "ddrr_common.h"
@@ -37,6 +44,16 @@ DDRR_HD unsigned rec_off01(unsigned r) {
 }
 DDRR_HD unsigned rec_off4(unsigned r) {
     return (r >> 4) * (unsigned)kRecBlockFloats + 64u + (r & 15u);
+}
+
+// The half-wave exchange of the delivery, restated for the host (the kernel: one
+// v_permlane32_swap per value pair): lane `lane` of atomic instruction `instr` (0: X, 1: Y) adds
+// plane 2 * pair + `upper` of the hit that lane `src` of the batch holds, at rec_off01(r_src) +
+// 8 * upper + 16 * pair.  X carries the hits of lanes 0-31, Y those of lanes 32-63; the lower half
+// of an instruction carries plane 0 (2), the upper half plane 1 (3).
+DDRR_HD void rec_halfwave_source(int lane, int instr, int &src, int &upper) {
+    upper = lane >> 5;
+    src = (lane & 31) + 32 * instr;
 }
 
 // float index of (plane, ray); 64-bit ray index for the consumers
