@@ -30,10 +30,14 @@ from .polyrigid import (  # noqa: F401
 )
 from .pose import RigidTransform, convert  # noqa: F401
 from .reconstruction import (  # noqa: F401
+    Fista,
     Reconstruction,
     TotalVariation3d,
     VolumeAdam,
+    prox_total_variation_3d,
     total_variation_3d,
+    tv_divergence_adjoint,
+    tv_gradient_operator,
 )
 from .registration import GraphedIteration, LevenbergMarquardt, PoseAdam, Registration  # noqa: F401
 from .renderers import Siddon, Trilinear  # noqa: F401

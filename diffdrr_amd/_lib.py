@@ -34,6 +34,7 @@ WARP_ABI_VERSION = 1
 BSPLINE_ABI_VERSION = 1
 POLYRIGID_ABI_VERSION = 1
 JACOBIAN_ABI_VERSION = 1
+PROX_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -430,3 +431,35 @@ def get_jacobian_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _jacobian_lib = jacobian_library(JACOBIAN_LIB_PATH)
     return _jacobian_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_prox_hip.so
+# The proximal operator of the total variation with a box constraint: FISTA reconstruction's inner solver
+# (C ABI: include/diffdrr_prox_hip.h)
+PROX_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_prox_hip.so")
+PROX_HEADER = Header.read("diffdrr_prox_hip.h", "ddrr_prox", PROX_ABI_VERSION)
+_PROX_SIGNATURES, _PROX_RESTYPES, PROX_EXPORTS = PROX_HEADER.tables()
+PROX_TV_ISOTROPIC, PROX_TV_ANISOTROPIC, PROX_MAX_DIM = PROX_HEADER.constants(
+    "TV_ISOTROPIC", "TV_ANISOTROPIC", "MAX_DIM")
+
+
+def prox_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_prox_hip.h."""
+    return DdrrLibrary(path, PROX_HEADER)
+
+
+_prox_lib: DdrrLibrary | None = None
+
+
+def get_prox_lib() -> DdrrLibrary:
+    """The TV proximal operator library, loaded on first use.  Raises if it has not been built."""
+    global _prox_lib
+    if _prox_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(PROX_LIB_PATH):
+            raise RuntimeError(
+                f"{PROX_LIB_PATH} is missing: the TV proximal operator kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _prox_lib = prox_library(PROX_LIB_PATH)
+    return _prox_lib

@@ -2065,3 +2065,73 @@ def polyrigid_backward_volume(twists, grad_out, pitch=(1.0, 1.0, 1.0), padding="
     _launch_polyrigid("ddrr_polyrigid_backward_volume", grad_out.device, twists.data_ptr(), *grid, *dims, *h, pad,
                       grad_out.data_ptr(), out.data_ptr())
     return out
+
+
+# ------------------------------------------------- TV proximal operator (libdiffdrr_prox_hip.so)
+_PROX_MODES = {"isotropic": _lib.PROX_TV_ISOTROPIC, "anisotropic": _lib.PROX_TV_ANISOTROPIC}
+
+
+def _launch_prox(name, device, *args):
+    """:func:`_launch` through the TV proximal operator library."""
+    _launch_on(_lib.get_prox_lib(), name, device, args)
+
+
+def _query_prox(name, *args):
+    return _lib.get_prox_lib().query(name, *args)
+
+
+def _check_prox(b, lam, spacing, mode, iterations, lower, upper, dual, x_prev, beta):
+    """The domain of include/diffdrr_prox_hip.h, each condition by name -> (dims, spacing, mode code, lower,
+    upper) as the entry takes them."""
+    if not torch.is_tensor(b) or b.dim() != 3:
+        raise ValueError("prox_tv3d: a (Dx, Dy, Dz) volume expected")
+    _check_volume_like("prox_tv3d: b", b)
+    if not on_device(b):
+        raise ValueError("prox_tv3d: a volume on the GPU expected (prox_total_variation_3d serves the host)")
+    if mode not in _PROX_MODES:
+        raise ValueError(f"prox_tv3d: mode must be 'isotropic' or 'anisotropic', not {mode!r}")
+    spacing = tuple(float(s) for s in spacing)
+    if len(spacing) != 3 or not all(0.0 < s < float("inf") for s in spacing):
+        raise ValueError(f"prox_tv3d: spacing must be three positive numbers, not {spacing}")
+    if not 0.0 <= float(lam) < float("inf"):
+        raise ValueError(f"prox_tv3d: lam must be >= 0 and finite, not {lam}")
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError(f"prox_tv3d: iterations must be an integer >= 0, not {iterations}")
+    lo = float("-inf") if lower is None else float(lower)
+    hi = float("inf") if upper is None else float(upper)
+    if not lo <= hi:
+        raise ValueError(f"prox_tv3d: lower {lower} must be <= upper {upper}")
+    if max(b.shape) > _lib.PROX_MAX_DIM or b.numel() > 2**34:
+        raise ValueError(f"prox_tv3d: at most {_lib.PROX_MAX_DIM} voxels per axis and 2^34 in all, got {tuple(b.shape)}")
+    if (not torch.is_tensor(dual) or dual.dtype != torch.float32 or not dual.is_contiguous()
+            or tuple(dual.shape) != (3, *b.shape) or dual.device != b.device):
+        raise ValueError(f"prox_tv3d: dual must be a contiguous float32 tensor of shape {(3, *b.shape)} on {b.device}")
+    if x_prev is not None:
+        _check_volume_like("prox_tv3d: x_prev", x_prev, b)
+        if not float("-inf") < float(beta) < float("inf"):
+            raise ValueError(f"prox_tv3d: beta must be finite, not {beta}")
+    return tuple(int(d) for d in b.shape), spacing, _PROX_MODES[mode], lo, hi
+
+
+def prox_tv3d(b, lam, spacing=(1.0, 1.0, 1.0), mode="isotropic", iterations=20, lower=None, upper=None, dual=None,
+              x_prev=None, beta=0.0):
+    """``argmin_{lower <= x <= upper} 1/2 |x - b|^2 + lam TV(x)`` of a (Dx, Dy, Dz) fp32 volume on the device by
+    ``iterations`` fast-gradient-projection steps from the dual start ``dual`` (3, Dx, Dy, Dz), which is updated in
+    place to p_n (include/diffdrr_prox_hip.h ddrr_prox_tv3d: two passes per step, bitwise reproducible, no host
+    synchronisation) -> (x, y): with ``x_prev`` the last pass also writes ``y = x + beta (x - x_prev)``, else y is
+    None."""
+    if dual is None:
+        raise ValueError("prox_tv3d: dual is required (zeros for a cold start); it is updated in place")
+    dims, spacing, code, lo, hi = _check_prox(b, lam, spacing, mode, iterations, lower, upper, dual, x_prev, beta)
+    dev = b.device
+    x = torch.empty_like(b)
+    y = torch.empty_like(b) if x_prev is not None else None
+    if b.numel() == 0:
+        return x, y
+    n = int(_query_prox("ddrr_prox_workspace_bytes", *dims, int(iterations))) if float(lam) > 0.0 else 0
+    if n < 0:
+        raise ValueError(f"prox_tv3d: no workspace for a volume of {dims}")
+    scratch = torch.empty(n // 4, dtype=torch.float32, device=dev) if n else None
+    _launch_prox("ddrr_prox_tv3d", dev, b.data_ptr(), *dims, *spacing, code, float(lam), int(iterations), lo, hi,
+                 dual.data_ptr(), _ptr(scratch), n, x.data_ptr(), _ptr(x_prev), float(beta), _ptr(y))
+    return x, y
