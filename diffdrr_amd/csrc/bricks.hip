@@ -483,8 +483,12 @@ __global__ __launch_bounds__(kBrickThreads) void siddon_brick_kernel(
         const float wmax = __uint_as_float((unsigned)p.work[1]);
         const float n_sum = reinterpret_cast<const float *>(p.work)[2];
         // (the channel gradient keeps the voxel's label in the word's low byte: 24 bits)
-        if (wmax > 0.f && wmax < 1e30f && n_sum > 0.f && n_sum <= 16384.f)
+        if (wmax > 0.f && wmax < 1e30f && n_sum > 0.f && n_sum <= 16384.f) {
             fixq = (GRADL ? 7.8e6f : 2.0e9f) / (n_sum * wmax);
+            // (n_sum wmax below ~6e-30: the scale overflows, every add would saturate and 1 / q store
+            // zeros -- float accumulators, as for wmax >= 1e30 at the other end)
+            if (!(fixq < INFINITY)) fixq = 0.f;
+        }
     }
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
     if (GRAD && (p.dbg & (1 << 23))) fixq = -fixq;  // (LdsAbsAddT: plain stores)
@@ -935,12 +939,18 @@ __global__ __launch_bounds__(kBlock) void volgrad_prepare_kernel(
         const float c = tri ? (3.4642f / dn + step) : 1.7321f / dn;
         float g = 0.f;
         if (n_channels > 0) {  // (B, C, N): the largest weight any label of the ray's column carries
-            for (int ch = 0; ch < n_channels; ++ch)
-                g = fmaxf(g, fabsf(grad_out[((long)b * n_channels + ch) * N + n]));
+            for (int ch = 0; ch < n_channels; ++ch) {
+                const float a = fabsf(grad_out[((long)b * n_channels + ch) * N + n]);
+                g = a == a ? fmaxf(g, a) : INFINITY;  // (fmaxf would drop a NaN)
+            }
         } else {
             g = fabsf(grad_out[r]);
         }
-        wmax = fmaxf(wmax, g * L * c);
+        // A weight that is not finite has no bound: the launch takes the float path, where a NaN or an
+        // infinity of grad_out reaches the voxels of its ray as it does in the per-ray kernels (fmaxf drops
+        // a NaN, and the fixed point would convert it to a count of 0: a finite gradient).
+        const float w = g * L * c;
+        wmax = fmaxf(wmax, w == w ? w : INFINITY);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));

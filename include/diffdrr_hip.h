@@ -177,7 +177,32 @@ int ddrr_siddon_forward_bricks_masked(const float *volume, int dx, int dy, int d
  * every ray of every pose that crosses it and STORED once -- no global atomics, no
  * zero-fill by the caller; g_volume (dx, dy, dz) is fully written.  Replaces
  * grid_sampler_3d_backward (nearest) behind renderers.py:159-164 like
- * ddrr_siddon_backward_volume, which remains the entry for arbitrary ray lists. */
+ * ddrr_siddon_backward_volume, which remains the entry for arbitrary ray lists.
+ *
+ * Precision (this entry, ddrr_trilinear_backward_volume_bricks and the two *_channels_volume_bricks
+ * entries; held per voxel against a float64 walk by tests/test_gpu_volume_gradient_bricks.py):
+ *  - the brick is accumulated as int32 FIXED POINT.  A prologue kernel bounds one contribution (wmax: max
+ *    over rays of |grad_out| img times the longest segment -- the largest weight of a marcher's samples --
+ *    in one voxel) and the number of contributions a voxel can receive (n_sum: per pose, the rays whose
+ *    pixels lie in a voxel's shadow, rounded up to a whole number and summed over the poses); one quantum
+ *    is n_sum * wmax / 2.0e9 (/ 7.8e6 for ddrr_siddon_backward_channels_volume_bricks, whose words also
+ *    hold the voxel's label), so no sum can wrap.  Every add is rounded to the nearest quantum: on top of
+ *    what float32 ray arithmetic loses anyway, a voxel is off by at most (its hits) x half a quantum;
+ *  - the quantum is ABSOLUTE, relative to the largest sum any voxel of the launch could receive, not to
+ *    the voxel's own value.  Voxels crossed only by rays whose grad_out is 1e4 times fainter than the
+ *    brightest pixel's (a hot pixel, a residual image with an outlier) keep about four digits fewer, and
+ *    contributions below half a quantum are lost.  Measured on the tests' three-pose scene, as the error of
+ *    such voxels relative to their own largest value: rays 1e4 times fainter 7e-4 (Siddon) and 1e-2
+ *    (marcher), 0.24 with the 23 bits of the Siddon channel entry; rays 1e6 times fainter 0.1 .. 1.  The
+ *    per-ray entries (float atomics) keep float32's relative precision, 1e-5, in the same voxels;
+ *  - FLOAT accumulators (LDS float atomics, several times slower; sums depend on the order of the adds)
+ *    take over where there is no usable bound: a source inside or within one voxel of the volume, n_sum >
+ *    16384, grad_out all zero, any weight |grad_out| img that is NaN or infinite (it then reaches the
+ *    voxels of its ray as in the per-ray entries), wmax >= 1e30, or n_sum * wmax so small (< ~6e-30) that
+ *    the scale 2.0e9 / (n_sum * wmax) is not a finite float;
+ *  - on the fixed-point path two launches of the same arguments agree bit for bit, on any stream;
+ *  - for diagnosis: after the call's work is done, words 1 and 2 of launch_ws hold wmax and n_sum as
+ *    floats (word 0 is the brick counter). */
 int ddrr_siddon_backward_volume_bricks(int dx, int dy, int dz, const float *source,
                                        const float *target, const float *img,
                                        const float *grad_out, int B, int det_h, int det_w,
@@ -287,7 +312,10 @@ int ddrr_trilinear_backward_channels_bricks(const float *volume, const unsigned 
  * ddrr_siddon_backward_channels).  The brick in LDS is the accumulator, 24-bit fixed point over the
  * voxel's label in the word's low byte (the label plane has no room of its own next to it); poses
  * whose source lies in or next to the volume -- no bound on a voxel's sum -- accumulate in fp32
- * and look the labels up in the label map.  B * C * N < 2^30, N < 2^22. */
+ * and look the labels up in the label map.  B * C * N < 2^30, N < 2^22.
+ * Precision: see ddrr_siddon_backward_volume_bricks; here wmax takes the largest |grad_out| over the
+ * channels of a pixel and the quantum is n_sum * wmax / 7.8e6 -- rays 1e4 times fainter than the
+ * brightest give 0.  The same float fallback, and the bound in words 1 and 2 of launch_ws. */
 int ddrr_siddon_backward_channels_volume_bricks(const unsigned char *labels, int dx, int dy, int dz,
                                                 const float *source, const float *target,
                                                 const float *img, const float *grad_out, int B,
@@ -298,7 +326,9 @@ int ddrr_siddon_backward_channels_volume_bricks(const unsigned char *labels, int
 /* The same for the marcher's channel render (renderers.py:242-252): g_volume[x] = sum over poses,
  * rays and samples of (trilinear weight of corner x) img step grad_out[b, label of the sample's
  * nearest voxel, n], on the owner bricks of ddrr_trilinear_backward_volume_bricks (31-bit fixed-point
- * accumulators; the labels are read from the label map).  STORED. */
+ * accumulators; the labels are read from the label map).  STORED.
+ * Precision, float fallback and the bound in launch_ws: see ddrr_siddon_backward_volume_bricks (quantum
+ * n_sum * wmax / 2.0e9, wmax from the largest |grad_out| over the channels of a pixel). */
 int ddrr_trilinear_backward_channels_volume_bricks(const unsigned char *labels, int dx, int dy,
                                                    int dz, const float *source, const float *target,
                                                    const float *img, const float *grad_out, int B,
@@ -404,6 +434,10 @@ int ddrr_trilinear_backward_rays(const float *aux, const float *grad_out, const 
                                  int n_points, const float *alphamin, const float *alphamax,
                                  float *g_source, float *g_target, float *g_img, float *g_alpha,
                                  void *stream);
+/* Volume gradient of the detector-grid march on owner bricks (32^3 voxels accumulated in LDS, STORED: no
+ * zero fill by the caller).  Precision, float fallback and the bound in words 1 and 2 of launch_ws: see
+ * ddrr_siddon_backward_volume_bricks -- a marcher's voxel receives ~100 corner weights, each rounded to
+ * the quantum n_sum * wmax / 2.0e9. */
 int ddrr_trilinear_backward_volume_bricks(int dx, int dy, int dz, const float *source,
                                           const float *target, const float *img,
                                           const float *grad_out, int B, int det_h, int det_w,
