@@ -17,6 +17,25 @@ using namespace ddrr;
 
 constexpr int kQueueCap = 128;  // entries per wave and length class (63 waiting + 64 arriving)
 constexpr int kBuckets = 3;     // length classes
+// Float record, bricks_fwd.hip: a hit's length class is the largest estimate over its run of
+// kRecordGroup adjacent lanes (8, 4, 2; 1: its own), and candidate rows start and end on multiples
+// of kRecordAlign pixels (align_pixbox_rows).  Wide runs keep the lines of the record whole in one
+// batch (fewer requests), narrow ones keep short hits out of long batches (fewer wave-steps).
+// 4 | 4: -4.8 % instructions, +25 % requests, the step -1.0 ... -1.7 %; at 2 and 1 the requests (+47 %,
+// +61 %) cost 0.15 and 0.28 ms more than the walk gains (profiles/r08/record_grouping.txt).
+// Tools builds choose with -DDDRR_RECORD_GROUP=n -DDDRR_RECORD_ALIGN=n; the product has one value.
+#if defined(DDRR_EXPERIMENTS) && defined(DDRR_RECORD_GROUP)
+constexpr int kRecordGroup = DDRR_RECORD_GROUP;
+#else
+constexpr int kRecordGroup = 4;
+#endif
+#if defined(DDRR_EXPERIMENTS) && defined(DDRR_RECORD_ALIGN)
+constexpr int kRecordAlign = DDRR_RECORD_ALIGN;
+#else
+constexpr int kRecordAlign = 4;
+#endif
+static_assert(kRecordGroup == 8 || kRecordGroup == 4 || kRecordGroup == 2 || kRecordGroup == 1, "DPP maxima");
+static_assert(kRecordAlign == 8 || kRecordAlign == 4 || kRecordAlign == 2 || kRecordAlign == 1, "a power of two, at most a run of the record");
 
 struct BrickArgs {
     const float *vol;
@@ -138,7 +157,8 @@ __device__ __forceinline__ void halfwave_swap(unsigned a, unsigned b, unsigned &
 
 // The float backward record of one batch of hits, delivered to the blocked layout of
 // record_layout.h.  Called by ALL lanes of the wave (ok: the lane holds a hit).  The batch's hits
-// are runs of up to 8 adjacent pixels (length classes are formed per run of 8) that start at ANY
+// are runs of up to 8 adjacent pixels (length classes are formed per run of 8; bricks_fwd.hip: per
+// run of kRecordGroup, so a run of 8 may come as two runs of 4 side by side) that start at ANY
 // lane -- the class queues are compacted -- so the two 32-byte halves of a run's line, planes 0 | 1
 // (2 | 3) of its rays, are brought into ONE instruction by a half-wave exchange: instruction X
 // carries plane 0 (2) of the hits of lanes 0-31 in its lower half and their plane 1 (3) in its

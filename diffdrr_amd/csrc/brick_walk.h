@@ -167,10 +167,12 @@ DDRR_HD int scatter_perm(int local, int k, int count, float inv_count) {
 // start and end on 8-pixel boundaries make every lane group of 8 one 32-byte-aligned run of each
 // plane -- 1.0 request per group and plane instead of 1.44 -- at the price of ~30 % more
 // candidates to test (measured: forward + record 2.00 -> 1.83 ms).
-DDRR_HD PixBox align_pixbox_rows(PixBox pb, int det_w) {
+// align: 8, or a narrower power of two (1: the box as it is) -- fewer candidates, runs that straddle.
+DDRR_HD PixBox align_pixbox_rows(PixBox pb, int det_w, int align = 8) {
     if (pb.j1 < pb.j0 || pb.i1 < pb.i0) return pb;
-    pb.j0 &= ~7;
-    pb.j1 = (pb.j1 | 7) < det_w ? (pb.j1 | 7) : det_w - 1;
+    const int m = align - 1;
+    pb.j0 &= ~m;
+    pb.j1 = (pb.j1 | m) < det_w ? (pb.j1 | m) : det_w - 1;
     return pb;
 }
 

@@ -727,7 +727,7 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
                 const PoseGrid pg = pose_grid(p.source + (long)(b0 + tid) * 3,
                                               p.target + (long)(b0 + tid) * N * 3, det_h, det_w);
                 PixBox pb = project_brick_grid(pg, det_h, det_w, cells, p.shift);
-                if (GROUPED && !(p.dbg & 1024)) pb = align_pixbox_rows(pb, det_w);
+                if (GROUPED && kRecordAlign > 1 && !(p.dbg & 1024)) pb = align_pixbox_rows(pb, det_w, kRecordAlign);
                 rows[tid] = fwd_row(brick_row(pg, pb, cells, p.shift, p.eps, 0.f));
             }
             if (tid == 0) counter[0] = 0;
@@ -795,15 +795,18 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
                     // bit is not set are no candidates -- the walks, the ray loads and the atomics of
                     // nine tenths of the rays at p_subsample = 0.1
                     if constexpr (SUB) hit = hit && ((p.pix_mask[pix >> 5] >> (pix & 31)) & 1u) != 0u;
-                    // float record: classes per run of 8 adjacent pixels (see bricks.hip)
+                    // float record: classes per run of kRecordGroup adjacent pixels (see bricks.hip)
                     float n_grp = hit ? n_est : 0.f;
                     if (GROUPED) {
-                        n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                            0, __builtin_bit_cast(int, n_grp), 0xB1, 0xf, 0xf, true)));   // lane ^ 1
-                        n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                            0, __builtin_bit_cast(int, n_grp), 0x4E, 0xf, 0xf, true)));   // lane ^ 2
-                        n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                            0, __builtin_bit_cast(int, n_grp), 0x141, 0xf, 0xf, true)));  // 7 - lane
+                        if constexpr (kRecordGroup >= 2)
+                            n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+                                0, __builtin_bit_cast(int, n_grp), 0xB1, 0xf, 0xf, true)));   // lane ^ 1
+                        if constexpr (kRecordGroup >= 4)
+                            n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+                                0, __builtin_bit_cast(int, n_grp), 0x4E, 0xf, 0xf, true)));   // lane ^ 2
+                        if constexpr (kRecordGroup >= 8)
+                            n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+                                0, __builtin_bit_cast(int, n_grp), 0x141, 0xf, 0xf, true)));  // 7 - lane
                     }
                     const bool c0 = n_grp < p.t1, c1 = !c0 && n_grp < p.t2;
                     const unsigned long long m0 = __ballot(hit && c0);

@@ -7,7 +7,11 @@ never are).  Nothing here runs on a GPU.
 Modelled, for the poses and the detector of ``bench.py`` (``bench.perturbed_poses``):
   * project_brick_grid, align_pixbox_rows, brick_row and brick_candidate (csrc/brick_walk.h) in
     float32, candidate by candidate;
-  * the length classes per run of 8 adjacent pixels at the thresholds 18 / 40;
+  * the length classes per run of ``--group`` adjacent lanes (csrc/brick_shared.h kRecordGroup) at the
+    thresholds ``--t1`` / ``--t2`` (22 / 48: what bricks_fwd.hip hands the 16-bit bricks), candidate rows
+    aligned to ``--align`` pixels (kRecordAlign);
+  * the walk: a batch takes as many wave-steps as its longest hit, estimated as n_est + 2; the live-lane
+    fraction is the hits' own crossings (n_est) over 64 lanes times the batches' steps;
   * the per-wave class queues (128 entries, compacted by lane rank, popped 64 from the top);
   * the pooled end of a brick (segments longest class first, cut into batches of 64);
   * the delivery, lane by lane: ``delivery_lanes`` is the restatement of
@@ -17,9 +21,11 @@ to the wave that has walked the fewest batches (ties: lowest wave), which is wha
 Every candidate that passes phase A counts as a hit (the kernel drops the few whose exact clip
 misses the brick; counters against the model: profiles/r07/record_delivery.txt).
 
-    python tools/record_requests.py [--poses 32] [--every 17]
-prints hits, batches, runs, the full-run fraction and the requests per launch of every delivery
-form, sampled over every ``--every``-th brick and scaled to all of them.
+    python tools/record_requests.py [--poses 32] [--every 17] [--group 4] [--align 4] [--t1 22] [--t2 48]
+prints units, hits, batches, wave-steps, the live-lane fraction, runs, the full-run fraction and the
+requests per launch of every delivery form, sampled over every ``--every``-th brick and scaled to all
+of them (profiles/r08/record_grouping.txt: the widths against the counters).  The defaults are the
+product's; ``--group 8 --align 8`` is the kernel of profiles/r07/record_delivery.txt.
 """
 import argparse
 import math
@@ -34,7 +40,7 @@ if ROOT not in sys.path:
 
 F = np.float32
 REC_BLOCK_FLOATS = 80
-QUEUE_CAP, WAVES, T1, T2 = 128, 16, 18.0, 40.0
+QUEUE_CAP, WAVES, T1, T2 = 128, 16, 22.0, 48.0  # (bricks_fwd.hip launch_fwd_bricks: the 16-bit storages)
 BRICK = (32, 32, 64)
 MARGIN, SHIFT, EPS = F(0.01), F(0.5), F(1e-8)
 
@@ -146,11 +152,12 @@ def project_brick_grid(g, H, W, lo, hi):
     return int(fi0), int(fi1), int(fj0), int(fj1)
 
 
-def align_pixbox_rows(pb, W):
+def align_pixbox_rows(pb, W, align=8):
     i0, i1, j0, j1 = pb
     if j1 < j0 or i1 < i0:
         return pb
-    return i0, i1, j0 & ~7, min(j1 | 7, W - 1)
+    m = align - 1
+    return i0, i1, j0 & ~m, min(j1 | m, W - 1)
 
 
 def brick_candidates(g, pb, lo, hi, W):
@@ -193,9 +200,10 @@ def cut_on_runs(L):
     return lanes, e
 
 
-def brick_batches(units, cut=False):
+def brick_batches(units, cut=False, group=8, t1=T1, t2=T2):
     """units: per unit of 64 candidates, (ray index, hit, n_est) arrays of at most 64 lanes.
     cut: batches end on run boundaries and have one at lanes 31 | 32 (cut_on_runs).
+    group: lanes per run that share a length class (the largest n_est of the run's hits).
     -> (batches: lists of ray indices in lane order, runs, full runs, hits)."""
     queues = [[[] for _ in range(3)] for _ in range(WAVES)]
     walked = [0] * WAVES
@@ -205,12 +213,12 @@ def brick_batches(units, cut=False):
         m = len(ray)
         n = np.zeros(64, F)
         n[:m] = np.where(hit, n_est, F(0))
-        grp = np.repeat(n.reshape(8, 8).max(1), 8)[:m]  # classes per run of 8 lanes
+        grp = np.repeat(n.reshape(64 // group, group).max(1), group)[:m]  # classes per run of `group` lanes
         per_run = np.add.reduceat(hit.astype(np.int64), np.arange(0, m, 8))
         runs += int((per_run > 0).sum())
         full += int((per_run == 8).sum())
         hits += int(hit.sum())
-        cls = np.where(grp < T1, 0, np.where(grp < T2, 1, 2))
+        cls = np.where(grp < t1, 0, np.where(grp < t2, 1, 2))
         for k in range(3):
             queues[wv][k].extend(ray[hit & (cls == k)].tolist())  # (lane_rank: compacted, lane order)
         walked[wv] += 1
@@ -260,37 +268,55 @@ def bench_rays(B, D=512, H=256):
     return s.reshape(B, 3).numpy().astype(F), t.reshape(B, H * H, 3).numpy().astype(F)
 
 
-def model(src, tgt, dims, H, W, every=17, forms=FORMS):
+def walk_steps(batches, steps_of):
+    """-> (wave-steps of the batches: each walks as long as its longest hit; the hits' own crossings).
+    steps_of: ray index -> estimated steps of the hit (n_est + 2: entry, exit and rounding)."""
+    wave, own = 0.0, 0.0
+    for bt in batches:
+        st = [steps_of[r] for r in bt if r >= 0]
+        wave += max(st)
+        own += sum(st) - 2.0 * len(st)
+    return wave, own
+
+
+def model(src, tgt, dims, H, W, every=17, forms=FORMS, group=8, align=8, t1=T1, t2=T2):
     B = src.shape[0]
     grids = [pose_grid(src[b], tgt[b], H, W) for b in range(B)]
     nb = [-(-dims[a] // BRICK[a]) for a in range(3)]
     n_bricks = nb[0] * nb[1] * nb[2]
-    tot = dict(hits=0, batches=0, runs=0, full=0, cut_batches=0, half_wave_cut=0, **{f: 0 for f in forms})
+    tot = dict(hits=0, batches=0, runs=0, full=0, cut_batches=0, half_wave_cut=0, units=0, wave_steps=0.0,
+               own_steps=0.0, **{f: 0 for f in forms})
     sampled = 0
     for brick in range(every // 2, n_bricks, every):
         bz, by, bx = brick % nb[2], (brick // nb[2]) % nb[1], brick // (nb[2] * nb[1])
         lo = [bx * BRICK[0], by * BRICK[1], bz * BRICK[2]]
         hi = [min(lo[a] + BRICK[a], dims[a]) for a in range(3)]
-        units = []
+        units, steps_of = [], {}
         for b in range(B):  # (B <= 32: one chunk)
-            pb = align_pixbox_rows(project_brick_grid(grids[b], H, W, lo, hi), W)
+            pb = align_pixbox_rows(project_brick_grid(grids[b], H, W, lo, hi), W, align)
             pix, hit, n_est = brick_candidates(grids[b], pb, lo, hi, W)
             ray = b * H * W + pix
             units += [(ray[k:k + 64], hit[k:k + 64], n_est[k:k + 64]) for k in range(0, len(ray), 64)]
-        batches, runs, full, hits = brick_batches(units)
+            steps_of.update(zip(ray[hit].tolist(), (n_est[hit] + F(2)).tolist()))
+        batches, runs, full, hits = brick_batches(units, group=group, t1=t1, t2=t2)
+        wave, own = walk_steps(batches, steps_of)
+        tot["units"] += len(units)
+        tot["wave_steps"] += wave
+        tot["own_steps"] += own
         tot["hits"] += hits
         tot["batches"] += len(batches)
         tot["runs"] += runs
         tot["full"] += full
         for f in forms:
             tot[f] += sum(batch_requests(np.asarray(bt, dtype=np.int64), f) for bt in batches)
-        cut = brick_batches(units, cut=True)[0]
+        cut = brick_batches(units, cut=True, group=group, t1=t1, t2=t2)[0]
         tot["cut_batches"] += len(cut)
         tot["half_wave_cut"] += sum(batch_requests(np.asarray(bt, dtype=np.int64), "half_wave") for bt in cut)
         sampled += 1
     scale = n_bricks / sampled
     res = {k: v * scale for k, v in tot.items()}
     res["full_fraction"] = tot["full"] / max(tot["runs"], 1)
+    res["live_lanes"] = tot["own_steps"] / max(64.0 * tot["wave_steps"], 1.0)
     res["floor"] = 2.5 * res["runs"]
     res["sampled_bricks"], res["bricks"] = sampled, n_bricks
     return res
@@ -302,12 +328,19 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--det", type=int, default=256)
     ap.add_argument("--every", type=int, default=17, help="model every n-th brick (odd: every brick row, column and layer is met)")
+    ap.add_argument("--group", type=int, default=4, choices=[8, 4, 2, 1], help="lanes per run that share a length class")
+    ap.add_argument("--align", type=int, default=4, choices=[8, 4, 2, 1], help="candidate rows start and end on multiples of this")
+    ap.add_argument("--t1", type=float, default=T1, help="length-class thresholds on n_est, as the kernel sees them")
+    ap.add_argument("--t2", type=float, default=T2)
     a = ap.parse_args()
     src, tgt = bench_rays(a.poses, a.size, a.det)
-    r = model(src, tgt, (a.size,) * 3, a.det, a.det, a.every)
-    print(f"{a.size}^3 -> {a.det}^2, {a.poses} poses, {r['sampled_bricks']} of {r['bricks']} bricks modelled; per launch:")
+    r = model(src, tgt, (a.size,) * 3, a.det, a.det, a.every, group=a.group, align=a.align, t1=a.t1, t2=a.t2)
+    print(f"{a.size}^3 -> {a.det}^2, {a.poses} poses, {r['sampled_bricks']} of {r['bricks']} bricks modelled; "
+          f"classes per run of {a.group}, rows aligned to {a.align}, thresholds {a.t1:g} / {a.t2:g}; per launch:")
+    print(f"  units                {r['units']:.3e}")
     print(f"  hits                 {r['hits']:.3e}")
     print(f"  batches              {r['batches']:.3e}")
+    print(f"  wave-steps           {r['wave_steps']:.3e}  (live lanes: {r['live_lanes']:.3f})")
     print(f"  runs                 {r['runs']:.3e}  (full: {100 * r['full_fraction']:.1f} %, "
           f"{r['hits'] / r['runs']:.2f} hits per run)")
     print(f"  requests, lane ^ 8 exchange (up to round 6)   {r['row_xor8']:.4e}  "
