@@ -928,7 +928,8 @@ __global__ __launch_bounds__(kBlock) void volgrad_prepare_kernel(
     const float *__restrict__ amax, int *__restrict__ work, int n_channels) {
     const int b = blockIdx.y;
     const float s[3] = {source[b * 3], source[b * 3 + 1], source[b * 3 + 2]};
-    const float step = tri ? (amax[0] - amin[0]) / (float)(n_points - 1) : 0.f;
+    // (|step|: with alphamax < alphamin the samples weigh a negative step, and the bound is on magnitudes)
+    const float step = tri ? fabsf(amax[0] - amin[0]) / (float)(n_points - 1) : 0.f;
     float wmax = 0.f;
     for (int n = blockIdx.x * kBlock + threadIdx.x; n < N; n += gridDim.x * kBlock) {
         const long r = (long)b * N + n;

@@ -63,6 +63,33 @@ DDRR_HD TriGeom tri_geom(const int lo[3], const BrickLayout &lay) {
 
 constexpr int TRI_AUX_PLANES = 7;  // sum T, sum dT (3), sum alpha dT (3)
 
+// The run of samples [m0, m1] of a ray that one brick looks at: those between the slab bounds `entry` and `exit` of
+// its box of base cells, with one sample of slack on both sides -- the membership test of the march is what decides.
+// A brick that the ray touches in ONE POINT (an edge or a corner shared with its neighbours) has entry == exit and
+// owns the sample that sits there; and the bounds (v_rcp_f32: 1 ulp, on index coordinates rounded to 2^-24 of the
+// source's) may come out a few ulps apart in EITHER order.  So a brick is passed over only when its bounds lie more
+// than half a sample spacing the wrong way round: rounding is orders of magnitude below that, and a brick that far
+// from the ray owns none of its samples.
+// span < 0 (alphamax < alphamin): the samples run from amin DOWN -- the same run with the two bounds' roles swapped.
+// span == 0: every sample sits at amin and weighs step = 0, but the record's sum of T is what d out / d alphamin and
+// d out / d alphamax are made of: all P samples are looked at.
+// false: no sample of the ray can fall in the box (also for NaN bounds).
+DDRR_HD bool tri_sample_run(float entry, float exit, float amin, float span, int P, int &m0, int &m1) {
+    const float gap = entry - exit;
+    if (span == 0.f) {
+        m0 = 0, m1 = P - 1;
+        return gap == gap;
+    }
+    const float sc = (float)(P - 1) / span;  // samples per unit of alpha, signed
+    if (!(gap * fabsf(sc) < 0.5f)) return false;
+    const float pe = (entry - amin) * sc, px = (exit - amin) * sc;
+    const float f0 = fminf(fmaxf(floorf(fminf(pe, px)) - 1.f, 0.f), (float)P);
+    const float f1 = fminf(fmaxf(ceilf(fmaxf(pe, px)) + 1.f, -1.f), (float)(P - 1));
+    if (!(f0 <= f1)) return false;
+    m0 = (int)f0, m1 = (int)f1;
+    return true;
+}
+
 // March one ray through one brick: sumT += T of every sample whose base corner is in the brick
 // (`acc(addr)` fetches a voxel of the LDS copy).  AUX: also the backward record of those
 // samples, rec = {sum dT_x, dT_y, dT_z, sum alpha dT_x, dT_y, dT_z} with dT the gradient of the
@@ -91,14 +118,9 @@ DDRR_HD bool tri_brick_march(const Acc &acc, float base, const TriGeom &G, const
         exit = fminf(exit, fmaxf(a1, a2));
     }
     const float span = amax - amin;
-    if (!(entry < exit) || !(span > 0.f)) return false;
-    const float lstep = 1.0f / (float)(P - 1), sc = (float)(P - 1) / span;
-    // samples that may fall in the brick: one of slack on both sides, the membership test
-    // below is what decides
-    const float f0 = fminf(fmaxf(floorf((entry - amin) * sc) - 1.f, 0.f), (float)P);
-    const float f1 = fminf(fmaxf(ceilf((exit - amin) * sc) + 1.f, -1.f), (float)(P - 1));
-    if (!(f0 <= f1)) return false;
-    const int m0 = (int)f0, m1 = (int)f1;
+    int m0, m1;
+    if (!tri_sample_run(entry, exit, amin, span, P, m0, m1)) return false;
+    const float lstep = 1.0f / (float)(P - 1);
     const float offc = fmaf(-G.lo[0], G.stridef[0],
                             fmaf(-G.lo[1], G.stridef[1], fmaf(-G.lo[2], G.stridef[2], base)));
     const float sx = G.stridef[0], sy = G.stridef[1];
@@ -188,12 +210,9 @@ DDRR_HD bool tri_brick_march_channels(const Acc &acc, float base, const TriGeom 
         exit = fminf(exit, fmaxf(a1, a2));
     }
     q.span = amax - amin;
-    if (!(entry < exit) || !(q.span > 0.f)) return false;
-    const float lstep = 1.0f / (float)(P - 1), sc = (float)(P - 1) / q.span;
-    const float f0 = fminf(fmaxf(floorf((entry - amin) * sc) - 1.f, 0.f), (float)P);
-    const float f1 = fminf(fmaxf(ceilf((exit - amin) * sc) + 1.f, -1.f), (float)(P - 1));
-    if (!(f0 <= f1)) return false;
-    const int m0 = (int)f0, m1 = (int)f1;
+    int m0, m1;
+    if (!tri_sample_run(entry, exit, amin, q.span, P, m0, m1)) return false;
+    const float lstep = 1.0f / (float)(P - 1);
     const float offc = fmaf(-G.lo[0], G.stridef[0],
                             fmaf(-G.lo[1], G.stridef[1], fmaf(-G.lo[2], G.stridef[2], base)));
     const float sx = G.stridef[0], sy = G.stridef[1];
@@ -274,12 +293,9 @@ DDRR_HD bool tri_brick_march_weighted(const Acc &acc, const Label &label, float 
         exit = fminf(exit, fmaxf(a1, a2));
     }
     q.span = amax - amin;
-    if (!(entry < exit) || !(q.span > 0.f)) return false;
-    const float lstep = 1.0f / (float)(P - 1), sc = (float)(P - 1) / q.span;
-    const float f0 = fminf(fmaxf(floorf((entry - amin) * sc) - 1.f, 0.f), (float)P);
-    const float f1 = fminf(fmaxf(ceilf((exit - amin) * sc) + 1.f, -1.f), (float)(P - 1));
-    if (!(f0 <= f1)) return false;
-    const int m0 = (int)f0, m1 = (int)f1;
+    int m0, m1;
+    if (!tri_sample_run(entry, exit, amin, q.span, P, m0, m1)) return false;
+    const float lstep = 1.0f / (float)(P - 1);
     const float offc = fmaf(-G.lo[0], G.stridef[0],
                             fmaf(-G.lo[1], G.stridef[1], fmaf(-G.lo[2], G.stridef[2], base)));
     const float sx = G.stridef[0], sy = G.stridef[1];
@@ -369,7 +385,7 @@ DDRR_HD MarchGrad trilinear_backward_from_record(float sumT, const float A[3], c
         Cd = fmaf(A[a], d, Cd);
         Bd = fmaf(Bv[a], d, Bd);
     }
-    const float Cu = span > 0.f ? (Bd - amin * Cd) / span : 0.f;  // sum u (dT . d)
+    const float Cu = span != 0.f ? (Bd - amin * Cd) / span : 0.f;  // sum u (dT . d); alphamax < alphamin too
     const float ws = gl * sumT / (float)(P - 1);  // through step = (amax - amin)/(P-1)
     r.g_amin = k * (Cd - Cu) - ws;
     r.g_amax = k * Cu + ws;
@@ -429,12 +445,9 @@ DDRR_HD void tri_owner_scatter(const Acc &acc, float base, const float lo[3], co
         exit = fminf(exit, fmaxf(a1, a2));
     }
     const float span = amax - amin;
-    if (!(entry < exit) || !(span > 0.f)) return;
-    const float lstep = 1.0f / (float)(P - 1), sc = (float)(P - 1) / span;
-    const float f0 = fminf(fmaxf(floorf((entry - amin) * sc) - 1.f, 0.f), (float)P);
-    const float f1 = fminf(fmaxf(ceilf((exit - amin) * sc) + 1.f, -1.f), (float)(P - 1));
-    if (!(f0 <= f1)) return;
-    const int m0 = (int)f0, m1 = (int)f1;
+    int m0, m1;
+    if (!tri_sample_run(entry, exit, amin, span, P, m0, m1)) return;
+    const float lstep = 1.0f / (float)(P - 1);
     const float offc = fmaf(-lo[0], stridef[0], fmaf(-lo[1], stridef[1], fmaf(-lo[2], stridef[2], base)));
     const float sx = stridef[0], sy = stridef[1];
     const float ws = acc_scale(acc, w, 0);
@@ -481,12 +494,9 @@ DDRR_HD void tri_owner_scatter_weighted(const Acc &acc, const Label &label, cons
         exit = fminf(exit, fmaxf(a1, a2));
     }
     q.span = amax - amin;
-    if (!(entry < exit) || !(q.span > 0.f)) return;
-    const float lstep = 1.0f / (float)(P - 1), sc = (float)(P - 1) / q.span;
-    const float f0 = fminf(fmaxf(floorf((entry - amin) * sc) - 1.f, 0.f), (float)P);
-    const float f1 = fminf(fmaxf(ceilf((exit - amin) * sc) + 1.f, -1.f), (float)(P - 1));
-    if (!(f0 <= f1)) return;
-    const int m0 = (int)f0, m1 = (int)f1;
+    int m0, m1;
+    if (!tri_sample_run(entry, exit, amin, q.span, P, m0, m1)) return;
+    const float lstep = 1.0f / (float)(P - 1);
     const float offc = fmaf(-lo[0], stridef[0], fmaf(-lo[1], stridef[1], fmaf(-lo[2], stridef[2], base)));
     const float sx = stridef[0], sy = stridef[1];
     int cur = -1;

@@ -405,7 +405,15 @@ int ddrr_trilinear_forward_channels(const float *volume, const unsigned char *la
  * 32^3 voxel bricks that OWN their voxels (a sample is visited by every brick owning one of
  * its 8 corners), accumulated in LDS and stored once -- no global atomics.
  * Replace renderers.py:205-241 and grid_sampler_3d_backward (bilinear) like the two
- * entries above, which remain the path for arbitrary ray lists and other modes. */
+ * entries above, which remain the path for arbitrary ray lists and other modes.
+ * The marching range is the caller's, in any order: the samples sit at alphamin + u_m (alphamax -
+ * alphamin) and weigh step = (alphamax - alphamin) / (n_points - 1) in every entry of the marcher,
+ * per-ray or on bricks.  alphamax < alphamin: the samples run backwards and the integral, its record
+ * and its gradients take the sign of the negative step, as the reference's formula does.
+ * alphamax == alphamin: out, g_source, g_target, g_img and g_volume are zeros; the record still holds
+ * the n_points equal samples, so g_alpha = (-1, +1) grad_out img sum T / (n_points - 1).
+ * Every sample is counted by exactly one brick, also one that sits on a face, an edge or a corner
+ * shared by several bricks. */
 int ddrr_trilinear_forward_bricks(const float *volume, int dx, int dy, int dz,
                                   const float *source, const float *target, const float *img,
                                   int B, int det_h, int det_w, float voxel_shift, float eps,
