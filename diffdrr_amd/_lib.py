@@ -128,6 +128,7 @@ REC_BLOCK_RAYS, REC_BLOCK_FLOATS = HEADER.constants("REC_BLOCK_RAYS", "REC_BLOCK
 # how a brick is held in LDS (ddrr_siddon_forward_bricks); BRICKS_CLEARED is a bit of ranges_valid
 BRICKS_F32, BRICKS_Q16, BRICKS_Q16_PACKED, BRICKS_CLEARED = HEADER.constants(
     "BRICKS_F32", "BRICKS_Q16", "BRICKS_Q16_PACKED", "BRICKS_CLEARED")
+BRICKS_Q16_Y, BRICKS_Q16_PACKED_Y = HEADER.constants("BRICKS_Q16_Y", "BRICKS_Q16_PACKED_Y")  # 32 x 64 x 32 bricks
 PACKED_AUX_PLANES, TRI_AUX_PLANES = HEADER.constants("PACKED_AUX_PLANES", "TRI_AUX_PLANES")
 
 

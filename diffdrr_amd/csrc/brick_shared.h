@@ -23,19 +23,27 @@ constexpr int kBuckets = 3;     // length classes
 // batch (fewer requests), narrow ones keep short hits out of long batches (fewer wave-steps).
 // 4 | 4: -4.8 % instructions, +25 % requests, the step -1.0 ... -1.7 %; at 2 and 1 the requests (+47 %,
 // +61 %) cost 0.15 and 0.28 ms more than the walk gains (profiles/r08/record_grouping.txt).
-// Tools builds choose with -DDDRR_RECORD_GROUP=n -DDDRR_RECORD_ALIGN=n; the product has one value.
+// The y-long bricks (32 x 64 x 32, FwdCfg::HAXIS == 1) have their own kRecordGroupY | kRecordAlignY and
+// thresholds.  On views along y they have 17 % fewer hits, batches and requests at 4 | 4; spending the
+// requests on 2 | 4 or 2 | 2 saves 4.5 % of the instructions as modelled and is SLOWER by 0.02 - 0.03 ms
+// (requests cost time below the knee too), so 4 | 4 stays, with thresholds 26 / 56 (-0.009 ms against
+// 22 / 48, four times the spread): profiles/r09/view_axis_bricks.txt.
+// Tools builds choose with -DDDRR_RECORD_GROUP=n -DDDRR_RECORD_ALIGN=n (both shapes); the product has
+// one value per shape.
 #if defined(DDRR_EXPERIMENTS) && defined(DDRR_RECORD_GROUP)
-constexpr int kRecordGroup = DDRR_RECORD_GROUP;
+constexpr int kRecordGroup = DDRR_RECORD_GROUP, kRecordGroupY = DDRR_RECORD_GROUP;
 #else
-constexpr int kRecordGroup = 4;
+constexpr int kRecordGroup = 4, kRecordGroupY = 4;
 #endif
 #if defined(DDRR_EXPERIMENTS) && defined(DDRR_RECORD_ALIGN)
-constexpr int kRecordAlign = DDRR_RECORD_ALIGN;
+constexpr int kRecordAlign = DDRR_RECORD_ALIGN, kRecordAlignY = DDRR_RECORD_ALIGN;
 #else
-constexpr int kRecordAlign = 4;
+constexpr int kRecordAlign = 4, kRecordAlignY = 4;
 #endif
-static_assert(kRecordGroup == 8 || kRecordGroup == 4 || kRecordGroup == 2 || kRecordGroup == 1, "DPP maxima");
-static_assert(kRecordAlign == 8 || kRecordAlign == 4 || kRecordAlign == 2 || kRecordAlign == 1, "a power of two, at most a run of the record");
+constexpr float kBrickT1Y = 26.f, kBrickT2Y = 56.f;  // (the z-long double bricks: 22 / 48)
+constexpr bool record_width_ok(int n) { return n == 8 || n == 4 || n == 2 || n == 1; }
+static_assert(record_width_ok(kRecordGroup) && record_width_ok(kRecordGroupY), "DPP maxima");
+static_assert(record_width_ok(kRecordAlign) && record_width_ok(kRecordAlignY), "a power of two, at most a run of the record");
 
 struct BrickArgs {
     const float *vol;
@@ -257,12 +265,13 @@ struct BrickLaunch {
 // voxels, take launch_bricks).
 // brick_ranges: the DDRR_BRICKS_Q16 workspace (header, (min, max) and fallback flag per brick),
 // ranges_valid: it already holds this volume's.
-// packed: the workspace also holds the bricks' LDS images (DDRR_BRICKS_Q16_PACKED) behind the ranges.
+// y_long: the 32 x 64 x 32 bricks (DDRR_BRICKS_Q16_Y / _PACKED_Y: views along y) instead of 32 x 32 x 64.
+// packed: the workspace also holds the bricks' LDS images (DDRR_BRICKS_Q16_PACKED[_Y]) behind the ranges.
 // clear, clear_n: floats the launch has to find zeroed (the image or the record its atomics add to):
 // cleared by the launch that clears the brick counter -- one launch instead of two memsets, each
 // of which is a launch of its own (5 us apiece in front of a 140 us one-pose render).
 struct FwdStorage {
-    int variant, packed;
+    int variant, packed, y_long;
     float *brick_ranges;
     int ranges_valid;
     float *clear;

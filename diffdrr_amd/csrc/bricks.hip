@@ -1343,8 +1343,9 @@ static int siddon_forward_bricks_impl(const float *volume, int dx, int dy, int d
     if (int rc = check_detector(det_h, det_w)) return rc;
     if (!(record_vmax >= 0.f)) return fail(-1, "record_vmax must be >= 0");
     if (brick_storage != DDRR_BRICKS_F32 && brick_storage != DDRR_BRICKS_Q16 &&
-        brick_storage != DDRR_BRICKS_Q16_PACKED)
-        return fail(-1, "brick_storage must be DDRR_BRICKS_F32, DDRR_BRICKS_Q16 or DDRR_BRICKS_Q16_PACKED");
+        brick_storage != DDRR_BRICKS_Q16_PACKED && brick_storage != DDRR_BRICKS_Q16_Y &&
+        brick_storage != DDRR_BRICKS_Q16_PACKED_Y)
+        return fail(-1, "brick_storage must be DDRR_BRICKS_F32, DDRR_BRICKS_Q16[_Y] or DDRR_BRICKS_Q16_PACKED[_Y]");
     if (brick_storage != DDRR_BRICKS_F32 && !brick_ranges)
         return fail(-1, "DDRR_BRICKS_Q16 needs the brick_ranges workspace");
     if (B == 0) return 0;
@@ -1371,8 +1372,9 @@ static int siddon_forward_bricks_impl(const float *volume, int dx, int dy, int d
                            eps, l.rec_q, aux);
     }
     FwdStorage fs;
-    fs.packed = brick_storage == DDRR_BRICKS_Q16_PACKED;
-    fs.variant = fs.packed ? DDRR_BRICKS_Q16 : brick_storage;
+    fs.packed = brick_storage == DDRR_BRICKS_Q16_PACKED || brick_storage == DDRR_BRICKS_Q16_PACKED_Y;
+    fs.y_long = brick_storage == DDRR_BRICKS_Q16_Y || brick_storage == DDRR_BRICKS_Q16_PACKED_Y;
+    fs.variant = brick_storage == DDRR_BRICKS_F32 ? DDRR_BRICKS_F32 : DDRR_BRICKS_Q16;
     fs.brick_ranges = brick_ranges;
     fs.ranges_valid = ranges_valid & 1;
     fs.clear = packed || cleared ? nullptr : (aux ? aux : out);

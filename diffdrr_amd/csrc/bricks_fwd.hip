@@ -13,6 +13,9 @@
 //     LDS of a CU: 32 x 32 x 64 voxels in 130 KiB, 17 % fewer (ray, brick) pairs, i.e. less of
 //     the per-hit work (exact clip, ray loads, queueing, record atomics) per voxel visited:
 //     forward 1.30 -> 1.21 ms, forward + record 1.82 -> 1.70 ms at 512^3 / 32 poses;
+//     The double brick's long axis follows the view: 32 x 64 x 32 (CfgQ16Y64) for views along y,
+//     where a ray crosses a sixth fewer brick faces than through 32 x 32 x 64 (CfgQ16Z64): forward +
+//     record + NCC step 1.485 -> 1.443 ms (profiles/r09/view_axis_bricks.txt);
 //   * BX x BY x BZ, THREADS: brick extent and workgroup size.  Measured and not adopted
 //     (profiles/r03, tools builds keep them as variants): two 512-thread workgroups per CU on
 //     32^3 16-bit bricks or on 32 x 32 x 16 fp32 half bricks (their barrier waits halve, their
@@ -52,17 +55,28 @@ struct FwdCfg {
     static constexpr int QUEUE_BYTES = WAVES * kBuckets * kQueueCap * 4;
     // A 16-bit brick whose values the block quantisation would not keep (brick_step.h
     // q16_usable: range large against the smallest 4^3-block level, non-finite values) is
-    // rendered from the volume's own fp32 values instead: its two halves along z, one after
-    // the other, as fp32 bricks BX x BY x BZ/2 (rows and planes padded by one float) in the
-    // same LDS.  MIXED: the budget has the room (every product configuration; not two
+    // rendered from the volume's own fp32 values instead: its two halves along HAXIS -- the
+    // brick's long axis: y (1) for a brick that is longer along y than along z, else z (2) --
+    // one after the other, as fp32 bricks BX x HY x HZ (rows and planes padded by one float) in
+    // the same LDS.  MIXED: the budget has the room (every product configuration; not two
     // workgroups per CU).
-    static constexpr int HZ = BZ / 2;
-    static constexpr int FSY = HZ * 4 + 4, FSX = BY * FSY + 4;  // byte strides of a fallback half
+    static constexpr int HAXIS = BY_ > BZ_ ? 1 : 2;
+    static constexpr int HLEN = (HAXIS == 1 ? BY : BZ) / 2;  // a half's extent along HAXIS
+    static constexpr int HY = HAXIS == 1 ? BY / 2 : BY, HZ = HAXIS == 2 ? BZ / 2 : BZ;
+    static constexpr int FSY = HZ * 4 + 4, FSX = HY * FSY + 4;  // byte strides of a fallback half
     static constexpr int FALLBACK_BYTES = (BX * FSX + 15) / 16 * 16;
     static constexpr bool MIXED =
-        Q16 && HZ % 4 == 0 && (BX * BY * (HZ / 4)) % THREADS == 0 &&
+        Q16 && HZ % 4 == 0 && (BX * HY * (HZ / 4)) % THREADS == 0 &&
         FALLBACK_BYTES + QUEUE_BYTES + 16 + 8 * 20 * 4 <= LDS_BUDGET;
-    using Half = FwdCfg<BX_, BY_, BZ_ / 2, THREADS_, false>;  // (used where MIXED only)
+    using Half = FwdCfg<BX_, HY, HZ, THREADS_, false>;  // (used where MIXED only)
+    // Float record: run width and row alignment of the length classes (brick_shared.h), per shape;
+    // the class thresholds on the estimated crossing count (flat within 1.5 % around these,
+    // profiles/r03; 22 / 48 for the double 16-bit bricks, profiles/r09 for the y-long ones)
+    static constexpr int RECORD_GROUP = HAXIS == 1 ? kRecordGroupY : kRecordGroup;
+    static constexpr int RECORD_ALIGN = HAXIS == 1 ? kRecordAlignY : kRecordAlign;
+    static constexpr bool DOUBLE_Q16 = Q16 && BX == 32 && BY * BZ == 32 * 64;
+    static constexpr float T1 = DOUBLE_Q16 ? (HAXIS == 1 ? kBrickT1Y : 22.f) : 18.f;
+    static constexpr float T2 = DOUBLE_Q16 ? (HAXIS == 1 ? kBrickT2Y : 48.f) : 40.f;
     static constexpr int LDS_BRICK = MIXED && FALLBACK_BYTES > BRICK_BYTES ? FALLBACK_BYTES : BRICK_BYTES;
     // poses per row-table chunk: what the LDS left by the brick and the queues holds
     static constexpr int ROW_ROOM = (LDS_BUDGET - LDS_BRICK - QUEUE_BYTES - 48) / (20 * 4);
@@ -514,7 +528,7 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
     prof.start();
 #endif
     // the work item in hand (workgroup-uniform): a brick, or -- a 16-bit brick rendered from fp32
-    // values -- one of its `n_sub` halves along z, taken one after the other
+    // values -- one of its `n_sub` halves along C::HAXIS, taken one after the other
     int brick_id = 0, sub = 0, n_sub = 1, pose_lo = 0, pose_hi = p.B;
     bool f32_brick = !C::Q16;
     // Looking ahead (packed 16-bit bricks).  A brick's fixed latencies -- the claim's atomic, the
@@ -640,8 +654,9 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
             n_sub = 1;
             if (C::MIXED) {
                 f32_brick = stale || (known ? la_f32 : (p.fallback && p.fallback[brick_id] != 0));
-                const int z0 = (brick_id % nbz) * C::BZ;
-                n_sub = f32_brick && p.D.z - z0 > C::HZ ? 2 : 1;
+                // (what the volume holds of the brick along the axis of its halves)
+                const int a0 = C::HAXIS == 1 ? ((brick_id / nbz) % nby) * C::BY : (brick_id % nbz) * C::BZ;
+                n_sub = f32_brick && (C::HAXIS == 1 ? p.D.y : p.D.z) - a0 > C::HLEN ? 2 : 1;
             }
         }
         // the requests of this iteration's look-ahead (lane 0 of wave 1; published before the
@@ -678,8 +693,9 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
         DDRR_PROF(PROF_CLAIM);
         Box box = cfg_brick_box<C>(p.D, nby, nbz, brick_id);
         if (C::MIXED && f32_brick) {
-            box.lo[2] += sub * C::HZ;
-            box.hi[2] = box.lo[2] + C::HZ < box.hi[2] ? box.lo[2] + C::HZ : box.hi[2];
+            constexpr int A = C::HAXIS;
+            box.lo[A] += sub * C::HLEN;
+            box.hi[A] = box.lo[A] + C::HLEN < box.hi[A] ? box.lo[A] + C::HLEN : box.hi[A];
         }
         const BoxF cells = boxf(box);
         StepGeom SG;
@@ -727,7 +743,7 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
                 const PoseGrid pg = pose_grid(p.source + (long)(b0 + tid) * 3,
                                               p.target + (long)(b0 + tid) * N * 3, det_h, det_w);
                 PixBox pb = project_brick_grid(pg, det_h, det_w, cells, p.shift);
-                if (GROUPED && kRecordAlign > 1 && !(p.dbg & 1024)) pb = align_pixbox_rows(pb, det_w, kRecordAlign);
+                if (GROUPED && C::RECORD_ALIGN > 1 && !(p.dbg & 1024)) pb = align_pixbox_rows(pb, det_w, C::RECORD_ALIGN);
                 rows[tid] = fwd_row(brick_row(pg, pb, cells, p.shift, p.eps, 0.f));
             }
             if (tid == 0) counter[0] = 0;
@@ -795,16 +811,16 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
                     // bit is not set are no candidates -- the walks, the ray loads and the atomics of
                     // nine tenths of the rays at p_subsample = 0.1
                     if constexpr (SUB) hit = hit && ((p.pix_mask[pix >> 5] >> (pix & 31)) & 1u) != 0u;
-                    // float record: classes per run of kRecordGroup adjacent pixels (see bricks.hip)
+                    // float record: classes per run of C::RECORD_GROUP adjacent pixels (see bricks.hip)
                     float n_grp = hit ? n_est : 0.f;
                     if (GROUPED) {
-                        if constexpr (kRecordGroup >= 2)
+                        if constexpr (C::RECORD_GROUP >= 2)
                             n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
                                 0, __builtin_bit_cast(int, n_grp), 0xB1, 0xf, 0xf, true)));   // lane ^ 1
-                        if constexpr (kRecordGroup >= 4)
+                        if constexpr (C::RECORD_GROUP >= 4)
                             n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
                                 0, __builtin_bit_cast(int, n_grp), 0x4E, 0xf, 0xf, true)));   // lane ^ 2
-                        if constexpr (kRecordGroup >= 8)
+                        if constexpr (C::RECORD_GROUP >= 8)
                             n_grp = fmaxf(n_grp, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
                                 0, __builtin_bit_cast(int, n_grp), 0x141, 0xf, 0xf, true)));  // 7 - lane
                     }
@@ -940,8 +956,9 @@ siddon_fwd_brick_kernel(BrickArgs p, float *__restrict__ out, float *__restrict_
         } else if (C::MIXED && half_of >= 0) {
             if constexpr (C::MIXED) {
                 Box nbox = cfg_brick_box<C>(p.D, nby, nbz, half_of);
-                nbox.lo[2] += half_sub * C::HZ;
-                nbox.hi[2] = nbox.lo[2] + C::HZ < nbox.hi[2] ? nbox.lo[2] + C::HZ : nbox.hi[2];
+                constexpr int A = C::HAXIS;
+                nbox.lo[A] += half_sub * C::HLEN;
+                nbox.hi[A] = nbox.lo[A] + C::HLEN < nbox.hi[A] ? nbox.lo[A] + C::HLEN : nbox.hi[A];
                 pf.clear();
                 pf.template half<typename C::Half>(p, brick, nbox, tid_ld, true);
                 pf_kind = 2;
@@ -1234,13 +1251,15 @@ int launch_cfg(const BrickArgs &p, int dev, int n_cu, float *out, float *aux, hi
 
 // brick variants (DDRR_BRICKS_* of include/diffdrr_hip.h; the others exist in tools builds)
 using CfgF32 = FwdCfg<32, 32, 32, 1024, false>;        // DDRR_BRICKS_F32: 32^3 fp32
-using CfgQ16Z64 = FwdCfg<32, 32, 64, 1024, true>;      // DDRR_BRICKS_Q16: 32x32x64 16-bit
+using CfgQ16Z64 = FwdCfg<32, 32, 64, 1024, true>;      // DDRR_BRICKS_Q16[_PACKED]: 32x32x64 16-bit
+using CfgQ16Y64 = FwdCfg<32, 64, 32, 1024, true>;      // DDRR_BRICKS_Q16[_PACKED]_Y: 32x64x32 16-bit (views along y)
+static_assert(CfgQ16Z64::MIXED && CfgQ16Y64::MIXED && CfgQ16Y64::HAXIS == 1 && CfgQ16Z64::HAXIS == 2, "fp32 halves");
+static_assert(CfgQ16Y64::FALLBACK_BYTES == CfgQ16Z64::FALLBACK_BYTES, "the same image of a half");
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
 using CfgQ16x2 = FwdCfg<32, 32, 32, 512, true>;        // 32^3 16-bit, two workgroups per CU
 using CfgQ16x1 = FwdCfg<32, 32, 32, 1024, true>;       // 32^3 16-bit, one workgroup per CU
 using CfgF32Half = FwdCfg<32, 32, 16, 512, false, 0>;  // 32x32x16 fp32 halves, two workgroups
 using CfgQ16X64 = FwdCfg<64, 32, 32, 1024, true>;      // double bricks, 16-bit
-using CfgQ16Y64 = FwdCfg<32, 64, 32, 1024, true>;
 using CfgF32Y64 = FwdCfg<16, 64, 32, 1024, false>;     // anisotropic fp32 bricks
 using CfgF32X64 = FwdCfg<64, 16, 32, 1024, false>;
 using CfgF32Z64 = FwdCfg<16, 32, 64, 1024, false>;
@@ -1267,7 +1286,8 @@ bool order_bricks(BrickArgs &q, int BX, int BY, int BZ, int nby, int nbz, int n_
 }
 
 // bytes of the caller's brick workspace: the (min, max) pairs, 2 floats per 32^3 brick (any brick
-// grid fits), then, for the packed storage, the LDS images of the 32 x 32 x 64 bricks
+// grid fits), then, for the packed storages, the LDS images of the storage's bricks (32 x 32 x 64,
+// DDRR_BRICKS_Q16_PACKED_Y: 32 x 64 x 32)
 // layout: [header: 64 words, word 0 = bricks on the fp32 path, word 1 = bricks, word 2 = launches
 //          that found the volume changed under the workspace]
 //         [(min, max) per brick: room for every 32^3 brick] [fallback flag per brick: int]
@@ -1282,19 +1302,26 @@ static long ranges_bytes(int dx, int dy, int dz) {
     return kWsHeaderBytes + (n32_bricks(dx, dy, dz) * 3 * (long)sizeof(float) + 255) / 256 * 256 + kFingerprintBytes;
 }
 
+template <class C>
+static long packed_bytes(int dx, int dy, int dz) {
+    return (long)((dx + C::BX - 1) / C::BX) * ((dy + C::BY - 1) / C::BY) * ((dz + C::BZ - 1) / C::BZ) * C::BRICK_BYTES;
+}
+
 long brick_workspace_bytes(int dx, int dy, int dz, int brick_storage) {
     if (brick_storage == DDRR_BRICKS_F32) return 0;
     long n = ranges_bytes(dx, dy, dz);
-    if (brick_storage == DDRR_BRICKS_Q16_PACKED)
-        n += (long)((dx + CfgQ16Z64::BX - 1) / CfgQ16Z64::BX) * ((dy + CfgQ16Z64::BY - 1) / CfgQ16Z64::BY) *
-             ((dz + CfgQ16Z64::BZ - 1) / CfgQ16Z64::BZ) * CfgQ16Z64::BRICK_BYTES;
+    if (brick_storage == DDRR_BRICKS_Q16_PACKED) n += packed_bytes<CfgQ16Z64>(dx, dy, dz);
+    if (brick_storage == DDRR_BRICKS_Q16_PACKED_Y) n += packed_bytes<CfgQ16Y64>(dx, dy, dz);
     return n;
 }
 
 // One configuration's instantiation for this launch: with the record or without, all pixels or those
 // of the mask.  PRE: the instantiation whose first claim hides the fingerprint's round trip.
 template <class C, bool PRE = false>
-static int launch_variant(const BrickLaunch &l, const BrickArgs &p, int dev, int n_cu) {
+static int launch_variant(const BrickLaunch &l, const BrickArgs &args, int dev, int n_cu) {
+    BrickArgs p = args;
+    p.t1 = g_brick_t1 * (C::T1 / 18.f);
+    p.t2 = g_brick_t2 * (C::T2 / 40.f);
     if (p.pix_mask)
         return l.aux ? launch_cfg<true, C, PRE, true>(p, dev, n_cu, l.out, l.aux, l.st)
                      : launch_cfg<false, C, PRE, true>(p, dev, n_cu, l.out, l.aux, l.st);
@@ -1302,9 +1329,17 @@ static int launch_variant(const BrickLaunch &l, const BrickArgs &p, int dev, int
                  : launch_cfg<false, C, PRE, false>(p, dev, n_cu, l.out, l.aux, l.st);
 }
 
-// s.variant: DDRR_BRICKS_F32 (0) or DDRR_BRICKS_Q16 (1); tools builds know more (g_brick_variant)
+// A 16-bit configuration: PRE for launches of a few poses.
+template <class C>
+static int launch_q16(const BrickLaunch &l, const BrickArgs &p, int dev, int n_cu) {
+    return l.B <= 8 ? launch_variant<C, true>(l, p, dev, n_cu) : launch_variant<C>(l, p, dev, n_cu);
+}
+
+// s.variant: DDRR_BRICKS_F32 (0) or DDRR_BRICKS_Q16 (1; s.y_long: the 32 x 64 x 32 bricks); tools
+// builds know more (g_brick_variant)
 int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s) {
     int variant = s.variant, ranges_valid = s.ranges_valid;
+    bool y_long = s.y_long != 0, packed_ok = s.packed != 0;
     // (brick_range_kernel: 16-byte loads where the volume's rows are aligned, else dwords)
     const bool vec_ok = (l.dz & 3) == 0 && (reinterpret_cast<uintptr_t>(l.volume) & 15) == 0;
     // the staging reads quads of four voxels from dword-aligned addresses (quad_load)
@@ -1320,6 +1355,9 @@ int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s) {
         variant = g_brick_variant;
         if (variant != last_variant) ranges_valid = 0;  // (the variants differ in their brick grids)
         last_variant = variant;
+        y_long = false;
+        // (the caller's packed images are those of its storage's shape)
+        if (!(variant == DDRR_BRICKS_Q16 || variant == 5) && !(variant == 6 && s.y_long)) packed_ok = false;
         few_f32 = false;  // (the variant asked for)
     }
 #endif
@@ -1337,7 +1375,7 @@ int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s) {
     p.ranges = ws ? ws + kWsHeaderBytes / sizeof(float) : nullptr;
     p.fallback = ws ? reinterpret_cast<const int *>(p.ranges + 2 * n32_bricks(l.dx, l.dy, l.dz)) : nullptr;
     p.ranges_valid = ranges_valid;
-    p.packed = s.packed && ws ? reinterpret_cast<const unsigned char *>(ws) + ranges_bytes(l.dx, l.dy, l.dz)
+    p.packed = packed_ok && ws ? reinterpret_cast<const unsigned char *>(ws) + ranges_bytes(l.dx, l.dy, l.dz)
                               : nullptr;
     p.fingerprint = ws ? reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned char *>(ws) +
                                                             ranges_bytes(l.dx, l.dy, l.dz) - kFingerprintBytes)
@@ -1350,19 +1388,14 @@ int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s) {
     p.split_t = g_brick_split_t;
     p.split_s = g_brick_split_s;
 #endif
-    // (length-class thresholds: flat within 1.5 % around these, profiles/r03)
-    if (variant == DDRR_BRICKS_Q16 || variant == 5) {
-        p.t1 = g_brick_t1 * (22.f / 18.f);
-        p.t2 = g_brick_t2 * (48.f / 40.f);
-    }
+    // (the length-class thresholds are the configuration's: launch_variant)
     int dev = 0, n_cu = 0;
     if (int rc = brick_launch_resources(l, p, dev, n_cu, /*zero_work=*/false)) return rc;
     int rc = 0;
     switch (variant) {
         case DDRR_BRICKS_F32: rc = launch_variant<CfgF32>(l, p, dev, n_cu); break;
-        case DDRR_BRICKS_Q16:  // (PRE: a few poses)
-            rc = l.B <= 8 ? launch_variant<CfgQ16Z64, true>(l, p, dev, n_cu)
-                          : launch_variant<CfgQ16Z64>(l, p, dev, n_cu);
+        case DDRR_BRICKS_Q16:
+            rc = y_long ? launch_q16<CfgQ16Y64>(l, p, dev, n_cu) : launch_q16<CfgQ16Z64>(l, p, dev, n_cu);
             break;
 #if defined(DDRR_EXPERIMENTS) || defined(DDRR_BRICK_PROFILE)
         case 2: rc = launch_variant<CfgQ16x1>(l, p, dev, n_cu); break;
@@ -1370,7 +1403,7 @@ int launch_fwd_bricks(const BrickLaunch &l, const FwdStorage &s) {
         case 3: rc = launch_variant<CfgF32Half>(l, p, dev, n_cu); break;
         case 4: rc = launch_variant<CfgQ16X64>(l, p, dev, n_cu); break;
         case 5: rc = launch_variant<CfgQ16Z64>(l, p, dev, n_cu); break;  // (= DDRR_BRICKS_Q16)
-        case 6: rc = launch_variant<CfgQ16Y64>(l, p, dev, n_cu); break;
+        case 6: rc = launch_variant<CfgQ16Y64>(l, p, dev, n_cu); break;  // (= DDRR_BRICKS_Q16_Y)
         case 7: rc = launch_variant<CfgF32Y64>(l, p, dev, n_cu); break;
         case 8: rc = launch_variant<CfgF32X64>(l, p, dev, n_cu); break;
         case 9: rc = launch_variant<CfgF32Z64>(l, p, dev, n_cu); break;

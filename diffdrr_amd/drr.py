@@ -73,12 +73,25 @@ class DRR(nn.Module):
             self.renderer = Trilinear(voxel_shift, **renderer_kwargs)
         else:
             raise ValueError(f"renderer must be 'siddon' or 'trilinear', not {renderer}")
+        if isinstance(self.renderer, Siddon):
+            self.renderer.view_axis = self._view_axis()
         # compile_renderer asked torch.compile to fuse the reference's tensor program;
         # the renderer here already is one hand-written kernel, so the flag is a no-op.
         self.compile_renderer = compile_renderer
         self.reshape = reshape
         self.patch_size = patch_size
         self.checkpoint_gradients = checkpoint_gradients
+
+    def _view_axis(self):
+        """"x", "y" or "z": the voxel axis with the largest component of the identity pose's central ray
+        -- the detector's nominal axis (0, 0, 1) taken through ``reorient`` and ``affine_inverse`` -- which
+        decides the long axis of the renderer's 16-bit bricks (``Siddon.brick_axis`` = "auto").  Worked
+        out once, here, from the module's own matrices as they were built on the host."""
+        with torch.no_grad():
+            ends = torch.tensor([[[0.0, 0.0, 0.0], [0.0, 0.0, 1.0]]])
+            ends = self.affine_inverse(self.detector.reorient(ends))
+            d = (ends[0, 1] - ends[0, 0]).abs()
+        return "xyz"[int(torch.argmax(d))]
 
     # ------------------------------------------------------------ properties
     @property
@@ -341,7 +354,7 @@ class DRR(nn.Module):
         arithmetic as the differentiable path (four launches: pose, rays, clear, render); None
         where that path does not apply (then the caller takes the usual one)."""
         from .pose import _AXIS, _check_convention
-        from .renderers import _brick_storage
+        from .renderers import _brick_axis, _brick_storage
 
         r, det = self.renderer, self.detector
         B = rot.shape[0]
@@ -365,7 +378,8 @@ class DRR(nn.Module):
             # (the density tensor itself: its packed bricks are cached per tensor object and version)
             ops.siddon_forward_bricks(self.density, source, target, img, cfg["det"],
                                       voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-                                      storage=_brick_storage(self.density, cfg, B), out=out, launch_ws=launch_ws,
+                                      storage=_brick_storage(self.density, cfg, B),
+                                      axis=_brick_axis(self.density, cfg, B), out=out, launch_ws=launch_ws,
                                       cleared=True, pixel_mask=det.subsample_mask())
         if det.n_subsample is not None:  # (p_subsample: the scattered grid, see _reshape_fused)
             return _ScatteredGrid(out.unsqueeze(1))

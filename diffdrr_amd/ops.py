@@ -312,13 +312,18 @@ def record_planes(aux, B, N):
     return torch.cat([p03, blk[:, 4].reshape(1, -1)])[:, :R].reshape(5, B, N)
 
 
-_BRICK_STORAGE = {"f32": _lib.BRICKS_F32, "q16": _lib.BRICKS_Q16, "q16p": _lib.BRICKS_Q16_PACKED}
-_range_cache = {}  # (id(volume), storage) -> _Workspace
+_BRICK_STORAGE = {"f32": _lib.BRICKS_F32, "q16": _lib.BRICKS_Q16, "q16p": _lib.BRICKS_Q16_PACKED,
+                  "q16y": _lib.BRICKS_Q16_Y, "q16py": _lib.BRICKS_Q16_PACKED_Y}
+# the same storage on bricks whose long axis is y (32 x 64 x 32 instead of 32 x 32 x 64): a workspace of
+# its own -- the brick grid and the packed images differ with the shape
+_Y_TWIN = {"q16": "q16y", "q16p": "q16py"}
+_range_cache = {}  # (id(volume), storage) -> _Workspace; the storage's name carries the bricks' shape
+_launches = 0      # brick launches on a 16-bit storage so far (stamps _Workspace.used)
 
 
 class _Workspace:
     """Cache entry of :func:`brick_workspace`: the buffer and what it was built from."""
-    __slots__ = ("ref", "buf", "built_version", "built_ptr", "churn", "event", "stream")
+    __slots__ = ("ref", "buf", "built_version", "built_ptr", "churn", "event", "stream", "used")
 
     def __init__(self, ref, buf):
         self.ref, self.buf = ref, buf
@@ -326,6 +331,7 @@ class _Workspace:
         self.built_ptr = None      # ... and the address of the storage they were read from
         self.churn = 0             # rebuilds because the volume had changed
         self.event = self.stream = None  # end of the building launch, and the stream it ran on
+        self.used = 0              # the last launch that rendered from it (_launches)
 
 
 def _workspace_entry(volume, storage):
@@ -335,11 +341,20 @@ def _workspace_entry(volume, storage):
     return None
 
 
+def _used_entry(volume, storage):
+    """The entry the reporting functions mean by "q16" / "q16p": of the two shapes' workspaces of this
+    volume (``_Y_TWIN``), the one a launch rendered from last -- the renderer chooses the shape
+    (``Siddon.brick_axis``), its callers ask by the storage's name."""
+    ents = [e for e in (_workspace_entry(volume, s) for s in (storage, _Y_TWIN.get(storage))) if e is not None]
+    return max(ents, key=lambda e: e.used) if ents else None
+
+
 def brick_workspace(volume, storage="q16"):
     """Workspace of the 16-bit brick staging (include/diffdrr_hip.h DDRR_BRICKS_Q16 /
     _PACKED): a header, the bricks' (min, max) and fp32-fallback flags and, for "q16p", the
     bricks themselves as they lie in LDS (+52 % of the volume's bytes, held as long as the volume
-    tensor lives).  Cached per volume TENSOR and storage.  The kernel fills it on the first
+    tensor lives).  Cached per volume TENSOR and storage; "q16y" / "q16py" are the same storages on
+    32 x 64 x 32 bricks, each a workspace of its own.  The kernel fills it on the first
     launch after the volume changed (one pass over the volume); the launch that filled it
     reports so with :func:`brick_workspace_commit`, and only then do later calls get
     ``valid`` = 1 -- a call that returns early (empty batch) or fails leaves it unbuilt.
@@ -399,7 +414,7 @@ def invalidate_brick_workspace(volume):
     render rebuilds its cached 16-bit bricks (every storage).  Without this call such an edit is
     still rendered correctly -- the launch notices (:func:`brick_workspace`) and takes the fp32
     path for every brick -- but at the fp32 bricks' speed until the workspace is rebuilt."""
-    for storage in ("q16", "q16p"):
+    for storage in ("q16", "q16p", "q16y", "q16py"):
         ent = _workspace_entry(volume, storage)
         if ent is not None:
             ent.built_version = ent.built_ptr = None
@@ -408,8 +423,9 @@ def invalidate_brick_workspace(volume):
 def brick_workspace_stale(volume, storage):
     """How many launches found the volume changed under this built workspace (its fingerprint did
     not match: they rendered from the fp32 values); 0 for a workspace in step with its volume, None
-    if none is built.  Reads one word from the device (a host sync)."""
-    ent = _workspace_entry(volume, storage)
+    if none is built.  Reads one word from the device (a host sync).  "q16" / "q16p": of the shape last
+    rendered from (``_used_entry``)."""
+    ent = _used_entry(volume, storage)
     if ent is None or ent.built_version is None:
         return None
     return int(ent.buf[2:3].view(torch.int32).item())
@@ -417,8 +433,9 @@ def brick_workspace_stale(volume, storage):
 
 def workspace_churn(volume, storage):
     """How many times the workspace of this volume was rebuilt because the volume had changed
-    (0: built once): a volume that changes between renders gains nothing from a packed copy."""
-    ent = _workspace_entry(volume, storage)
+    (0: built once): a volume that changes between renders gains nothing from a packed copy.
+    "q16" / "q16p": of the shape last rendered from (``_used_entry``)."""
+    ent = _used_entry(volume, storage)
     return ent.churn if ent is not None else 0
 
 
@@ -426,8 +443,10 @@ def brick_fallbacks(volume, storage):
     """(bricks rendered from their own fp32 values, bricks) of the built workspace of this
     volume -- the 16-bit block quantisation is only used for bricks whose range is small against
     their level (csrc/brick_step.h q16_usable) -- or None if no launch has built it yet.
-    Reads two words from the device (a host sync)."""
-    ent = _workspace_entry(volume, storage)
+    Reads two words from the device (a host sync).  "q16" / "q16p" report the workspace a launch
+    rendered from last, whichever shape its bricks have (``_used_entry``: 32 x 32 x 64, or 32 x 64 x 32 where
+    ``Siddon.brick_axis`` chose "y"); "q16y" / "q16py" name the y-long one."""
+    ent = _used_entry(volume, storage)
     if ent is None or ent.built_version is None:
         return None
     head = ent.buf[:2].view(torch.int32).tolist()
@@ -454,7 +473,7 @@ def brick_record_buffer(B, N, device):
 
 def siddon_forward_bricks(volume, source, target, img, det, *, voxel_shift=0.5, eps=1e-8,
                           want_aux=False, record_vmax=0.0, storage="f32", want_image=True,
-                          aux=None, out=None, launch_ws=None, cleared=False, pixel_mask=None):
+                          aux=None, out=None, launch_ws=None, cleared=False, pixel_mask=None, axis="z"):
     """Detector-grid Siddon (sum) through the volume-stationary brick kernel: every 32^3
     brick is staged in LDS once and all rays of all poses are traced through it.
     Requires the targets to be the affine detector grid DRR builds.
@@ -464,7 +483,10 @@ def siddon_forward_bricks(volume, source, target, img, det, *, voxel_shift=0.5, 
     instead of 5, bit-reproducible; csrc/record_pack.h).
     ``storage``: "f32" stages the volume's own values in 32^3 bricks, "q16" a 16-bit block
     quantisation in 32 x 32 x 64 bricks, "q16p" the same bricks from a packed copy kept in the
-    cached workspace (include/diffdrr_hip.h DDRR_BRICKS_*).
+    cached workspace (include/diffdrr_hip.h DDRR_BRICKS_*).  ``axis`` = "y": the 16-bit storages on
+    32 x 64 x 32 bricks ("q16y" / "q16py", which can also be named directly; a workspace of their own) --
+    fewer (ray, brick) pairs where the rays run along y; on the device only (a CPU tensor, i.e. the host
+    emulation, keeps the z-long bricks), and without meaning for "f32".
     ``aux`` / ``out`` / ``launch_ws``: a record (:func:`brick_record_buffer`) or an image (B, N) and a
     launch workspace (:func:`launch_workspace`) the caller brings along; ``cleared``: what the
     launch's atomics add to (the record if one is wanted, else the image) and the workspace's
@@ -477,6 +499,10 @@ def siddon_forward_bricks(volume, source, target, img, det, *, voxel_shift=0.5, 
     H, W = _grid(det, N, source)
     if storage != "f32" and not brick_storage_applies(volume):
         storage = "f32"
+    if axis not in ("y", "z"):
+        raise ValueError(f"axis must be 'y' or 'z', not {axis!r}")
+    if axis == "y" and volume.device.type == "cuda":
+        storage = _Y_TWIN.get(storage, storage)
     # (want_image = False with want_aux: the record alone -- siddon_ncc_forward forms the image)
     need_out = want_image or not want_aux
     if out is not None and (not need_out or out.shape != (B, N) or out.dtype != torch.float32
@@ -508,8 +534,12 @@ def siddon_forward_bricks(volume, source, target, img, det, *, voxel_shift=0.5, 
         _ptr(out), _ptr(aux), float(record_vmax) if packed else 0.0,
         _BRICK_STORAGE[storage], _ptr(ranges), int(valid) | (_lib.BRICKS_CLEARED if cleared else 0),
         launch_ws.data_ptr(), *(() if pixel_mask is None else (pixel_mask.data_ptr(),)))
-    if storage != "f32" and not valid:
-        brick_workspace_commit(volume, storage)
+    if storage != "f32":
+        global _launches
+        _launches += 1
+        _workspace_entry(volume, storage).used = _launches
+        if not valid:
+            brick_workspace_commit(volume, storage)
     return out, aux
 
 

@@ -357,7 +357,7 @@ class LevenbergMarquardt:
     # -- one render of the current parameters with its record: the first two launches of a step
     def _render(self):
         from . import ops
-        from .renderers import _brick_storage
+        from .renderers import _brick_axis, _brick_storage
 
         drr, reg = self.reg.drr, self.reg
         r, det = drr.renderer, drr.detector
@@ -371,6 +371,7 @@ class LevenbergMarquardt:
                                                           clear_launch_ws=launch_ws)
         ops.siddon_forward_bricks(drr.density, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"],
                                   eps=cfg["eps"], want_aux=True, storage=_brick_storage(drr.density, cfg, self.B),
+                                  axis=_brick_axis(drr.density, cfg, self.B),
                                   want_image=False, aux=self._aux, launch_ws=launch_ws, cleared=True)
         return dict(aux=self._aux, source=source, Mw=Mw, Ainv=Ainv, P=P, rot=rot, xyz=xyz, axes=self.axes,
                     reorient34=reorient34), dict(eps=cfg["eps"], with_img_path=not cfg["stop_gradients"])

@@ -165,6 +165,45 @@ def _brick_storage(volume, cfg, poses=None):
     return storage
 
 
+# Whether Siddon.brick_axis = "auto" takes the y-long bricks on views along y: decided by the clock of
+# the headline step against the project's bar (profiles/r09/view_axis_bricks.txt).
+VIEW_AXIS_AUTO = True
+# ... and from how many poses per launch on.  At 1 - 2 poses the y-long bricks are 6 - 7 % SLOWER (a launch of a
+# pose or two is staging and latency, and the y-long image has more row padding; the phantom has 415
+# instead of 369 bricks on the fp32 path), at 4 - 8 level to +0.8 %, from 16 on ahead (same file, section 6).  A
+# module that renders one volume with few AND many poses per launch keeps a packed copy per shape.
+VIEW_AXIS_MIN_POSES = 16
+
+
+def _brick_axis(volume, cfg, poses=None):
+    """The long axis of the 16-bit bricks of a launch (Siddon.brick_axis): "y" (32 x 64 x 32) or "z"
+    (32 x 32 x 64).  "auto" takes the y-long bricks where the module's view runs along the volume's y
+    axis (``view_axis``, resolved once by DRR) -- and only for launches of at least VIEW_AXIS_MIN_POSES
+    poses of a volume on the device with at least 4 double bricks per CU: below that the storage is
+    chosen by the measured table above, which knows the z-long shape alone.  A CPU tensor (the host emulation) has the z-long bricks whatever is asked.
+    Without meaning for fp32 bricks: ops.siddon_forward_bricks ignores it there."""
+    dev = volume.device
+    if dev.type != "cuda" or volume.dim() != 3:
+        return "z"
+    if dev not in _cu_count:
+        _cu_count[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return _resolve_brick_axis(cfg.get("brick_axis", "z"), cfg.get("view_axis"), volume.shape, _cu_count[dev], poses)
+
+
+def _resolve_brick_axis(brick_axis, view_axis, shape, n_cu, poses=None):
+    """``_brick_axis`` for a volume of ``shape`` on a device of ``n_cu`` CUs: explicit "y" / "z" win;
+    "auto" is "y" for a view along y of a volume with at least 4 double bricks per CU, rendered with at
+    least VIEW_AXIS_MIN_POSES poses per launch (``poses`` = None: unknown, taken as enough), else "z"."""
+    if brick_axis in ("y", "z"):
+        return brick_axis
+    if brick_axis != "auto":
+        raise ValueError(f"Siddon.brick_axis must be 'auto', 'y' or 'z', not {brick_axis!r}")
+    if view_axis != "y" or not VIEW_AXIS_AUTO or (poses is not None and int(poses) < VIEW_AXIS_MIN_POSES):
+        return "z"
+    dx, dy, dz = shape
+    return "y" if (-(-dx // 32)) * (-(-dy // 64)) * (-(-dz // 32)) >= 4 * n_cu else "z"
+
+
 class _SiddonFn(torch.autograd.Function):
     """out (B,N) = img * sum_k V_k dalpha_k (or max_k).  Inputs: volume, source,
     target, img.  Backward: ddrr_siddon_backward_rays from the 8-float forward
@@ -184,7 +223,7 @@ class _SiddonFn(torch.autograd.Function):
             out, aux = ops.siddon_forward_bricks(
                 volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"],
                 eps=cfg["eps"], want_aux=want_aux, record_vmax=_record_vmax(volume, want_aux, cfg),
-                storage=_brick_storage(volume, cfg, source.shape[0]))
+                storage=_brick_storage(volume, cfg, source.shape[0]), axis=_brick_axis(volume, cfg, source.shape[0]))
         else:
             out, aux, _ = ops.siddon_forward(
                 volume, source, target, img, voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
@@ -454,7 +493,8 @@ class _SiddonPoseFn(torch.autograd.Function):
             out, aux = ops.siddon_forward_bricks(
                 volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"],
                 eps=cfg["eps"], want_aux=want_aux, record_vmax=_record_vmax(volume, want_aux, cfg),
-                storage=_brick_storage(volume, cfg, source.shape[0]), pixel_mask=cfg.get("pixel_mask"))
+                storage=_brick_storage(volume, cfg, source.shape[0]), axis=_brick_axis(volume, cfg, source.shape[0]),
+                pixel_mask=cfg.get("pixel_mask"))
         else:
             out, aux, _ = ops.siddon_forward(
                 volume, source, target, img, voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
@@ -514,7 +554,7 @@ class _EulerSiddonNccFn(torch.autograd.Function):
                                                           clear_launch_ws=launch_ws if some else None)
         ops.siddon_forward_bricks(
             volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-            want_aux=True, storage=_brick_storage(volume, cfg, B), want_image=False, aux=aux,
+            want_aux=True, storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=False, aux=aux,
             launch_ws=launch_ws, cleared=some)
         ncc, stats, _, total = ops.siddon_ncc_forward(aux, img, fixed, ncc_eps, want_sum=True) if reduce_sum \
             else (*ops.siddon_ncc_forward(aux, img, fixed, ncc_eps), None)
@@ -560,7 +600,8 @@ class _EulerSiddonImageFn(torch.autograd.Function):
                                                           clear=aux, clear_launch_ws=launch_ws)
         out, _ = ops.siddon_forward_bricks(
             volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-            want_aux=True, storage=_brick_storage(volume, cfg, B), aux=aux, launch_ws=launch_ws, cleared=True)
+            want_aux=True, storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), aux=aux,
+            launch_ws=launch_ws, cleared=True)
         ctx.axes, ctx.cfg = axes, cfg
         ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, Mw, source, aux)
         return out
@@ -709,6 +750,16 @@ class Siddon(torch.nn.Module):
         # and 256^3, 45 % SLOWER on the 133-slice example shape -- not kept,
         # profiles/r05/f32_packed_lookahead_experiment.txt.)
         self.brick_storage = "q16p"
+        # The long axis of the 16-bit bricks: "z" (32 x 32 x 64), "y" (32 x 64 x 32: a ray along y
+        # crosses half as many brick faces along its way -- 17 % fewer (ray, brick) pairs on the
+        # views of an AP / PA subject, DESIGN section 3.1 "Long axis along the view"), or "auto":
+        # "y" where the identity pose's central ray runs along the volume's y axis (``view_axis``, set
+        # by DRR from the subject's affine and orientation) for launches of 16 poses and more of a volume
+        # with at least 4 double bricks per CU (-4.4 % of the 32-pose step; a pose or two per launch is
+        # 6 % faster on the z-long bricks), else "z" (_brick_axis; there is no
+        # x-long shape).  Exact on any view; each shape in use keeps its own packed copy.
+        self.brick_axis = "auto"
+        self.view_axis = None
         # Under HIP-graph capture the 16-bit storages are only used if the caller promises that
         # the volume is not edited in place between replays (the graph bakes in the cached
         # workspace): otherwise captured renders use fp32 bricks, which read the live volume.
@@ -752,6 +803,7 @@ class Siddon(torch.nn.Module):
                 "det": self.detector_shape if det == "unchecked" else det, "tile": self.tile,
                 "path": self.grid_path,
                 "packed_record": self.packed_record, "storage": self.brick_storage,
+                "brick_axis": self.brick_axis, "view_axis": self.view_axis,
                 "static_volume": self.static_volume,
                 "channels_on_bricks": self.channels_on_bricks, "channel_words": self.channel_words}
 

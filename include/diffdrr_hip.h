@@ -125,6 +125,12 @@ int ddrr_siddon_forward(const float *volume, int dx, int dy, int dz, const float
  * a brick with a straight 16-byte copy of half the bytes instead of converting the fp32 volume
  * again -- what a volume that is rendered many times wants, most of all with few poses per
  * launch, where staging is most of the launch.
+ * DDRR_BRICKS_Q16_Y / DDRR_BRICKS_Q16_PACKED_Y: the same two storages on bricks whose long axis is
+ * y, 32 x 64 x 32 -- for views whose rays run mostly along y (an AP / PA subject), where a ray
+ * crosses a sixth fewer brick faces than through 32 x 32 x 64 ones.  Same guard, same bounds; a
+ * brick on the fp32 path is rendered as its two 32 x 32 x 32 halves along y.  Exact on any view,
+ * slower than the z-long bricks on views along z or x.  A workspace belongs to ONE brick_storage:
+ * the packed images and the brick grid differ with the shape.
  * (The 16-bit walk carries alpha pre-scaled by 2^64: rays with |alpha| >= 2^63 inside the volume
  * -- |t - s + eps| < ~1e-16 on an axis, which eps = 1e-8 excludes -- overflow to inf / NaN there,
  * where fp32 bricks would return a finite value.)
@@ -149,6 +155,8 @@ int ddrr_siddon_forward(const float *volume, int dx, int dy, int dz, const float
 #define DDRR_BRICKS_F32 0
 #define DDRR_BRICKS_Q16 1
 #define DDRR_BRICKS_Q16_PACKED 2
+#define DDRR_BRICKS_Q16_Y 3
+#define DDRR_BRICKS_Q16_PACKED_Y 4
 #define DDRR_BRICKS_CLEARED 2 /* (a bit of ranges_valid) */
 long ddrr_brick_workspace_bytes(int dx, int dy, int dz, int brick_storage);
 long ddrr_brick_launch_workspace_bytes(int dx, int dy, int dz);

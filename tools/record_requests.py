@@ -22,10 +22,12 @@ Every candidate that passes phase A counts as a hit (the kernel drops the few wh
 misses the brick; counters against the model: profiles/r07/record_delivery.txt).
 
     python tools/record_requests.py [--poses 32] [--every 17] [--group 4] [--align 4] [--t1 22] [--t2 48]
+                                    [--brick 32,32,64]
 prints units, hits, batches, wave-steps, the live-lane fraction, runs, the full-run fraction and the
 requests per launch of every delivery form, sampled over every ``--every``-th brick and scaled to all
 of them (profiles/r08/record_grouping.txt: the widths against the counters).  The defaults are the
-product's; ``--group 8 --align 8`` is the kernel of profiles/r07/record_delivery.txt.
+product's z-long bricks'; ``--group 8 --align 8`` is the kernel of profiles/r07/record_delivery.txt;
+``--brick 32,64,32 --t1 26 --t2 56`` the y-long configuration (profiles/r09/view_axis_bricks.txt).
 """
 import argparse
 import math
@@ -279,7 +281,9 @@ def walk_steps(batches, steps_of):
     return wave, own
 
 
-def model(src, tgt, dims, H, W, every=17, forms=FORMS, group=8, align=8, t1=T1, t2=T2):
+def model(src, tgt, dims, H, W, every=17, forms=FORMS, group=8, align=8, t1=T1, t2=T2, brick=BRICK):
+    """brick: the bricks' extent (BX, BY, BZ) -- 32 x 32 x 64, or 32 x 64 x 32 (the y-long configuration)."""
+    BRICK = tuple(brick)  # noqa: N806 (shadows the module's default on purpose)
     B = src.shape[0]
     grids = [pose_grid(src[b], tgt[b], H, W) for b in range(B)]
     nb = [-(-dims[a] // BRICK[a]) for a in range(3)]
@@ -332,10 +336,16 @@ def main():
     ap.add_argument("--align", type=int, default=4, choices=[8, 4, 2, 1], help="candidate rows start and end on multiples of this")
     ap.add_argument("--t1", type=float, default=T1, help="length-class thresholds on n_est, as the kernel sees them")
     ap.add_argument("--t2", type=float, default=T2)
+    ap.add_argument("--brick", default=",".join(map(str, BRICK)), help="the bricks' extent BX,BY,BZ (32,64,32: y-long)")
     a = ap.parse_args()
     src, tgt = bench_rays(a.poses, a.size, a.det)
-    r = model(src, tgt, (a.size,) * 3, a.det, a.det, a.every, group=a.group, align=a.align, t1=a.t1, t2=a.t2)
-    print(f"{a.size}^3 -> {a.det}^2, {a.poses} poses, {r['sampled_bricks']} of {r['bricks']} bricks modelled; "
+    brick = tuple(int(v) for v in a.brick.split(","))
+    if len(brick) != 3 or min(brick) < 1:
+        ap.error("--brick BX,BY,BZ")
+    r = model(src, tgt, (a.size,) * 3, a.det, a.det, a.every, group=a.group, align=a.align, t1=a.t1, t2=a.t2,
+              brick=brick)
+    print(f"{a.size}^3 -> {a.det}^2, {a.poses} poses, {r['sampled_bricks']} of {r['bricks']} bricks "
+          f"({brick[0]} x {brick[1]} x {brick[2]}) modelled; "
           f"classes per run of {a.group}, rows aligned to {a.align}, thresholds {a.t1:g} / {a.t2:g}; per launch:")
     print(f"  units                {r['units']:.3e}")
     print(f"  hits                 {r['hits']:.3e}")
