@@ -35,6 +35,7 @@ BSPLINE_ABI_VERSION = 1
 POLYRIGID_ABI_VERSION = 1
 JACOBIAN_ABI_VERSION = 1
 PROX_ABI_VERSION = 1
+WNCC_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -464,3 +465,35 @@ def get_prox_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _prox_lib = prox_library(PROX_LIB_PATH)
     return _prox_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_wncc_hip.so
+# Weighted (masked) NCC of image pairs and the registration step's epilogues with a per-pixel weight
+# (C ABI: include/diffdrr_wncc_hip.h)
+WNCC_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_wncc_hip.so")
+WNCC_HEADER = Header.read("diffdrr_wncc_hip.h", "ddrr_wncc", WNCC_ABI_VERSION)
+_WNCC_SIGNATURES, _WNCC_RESTYPES, WNCC_EXPORTS = WNCC_HEADER.tables()
+WNCC_GROUP_RAYS, WNCC_STATS, WNCC_SLOT_BYTES, WNCC_MAX_POSES = WNCC_HEADER.constants(
+    "GROUP_RAYS", "STATS", "SLOT_BYTES", "MAX_POSES")
+
+
+def wncc_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_wncc_hip.h."""
+    return DdrrLibrary(path, WNCC_HEADER)
+
+
+_wncc_lib: DdrrLibrary | None = None
+
+
+def get_wncc_lib() -> DdrrLibrary:
+    """The weighted NCC library, loaded on first use.  Raises if it has not been built."""
+    global _wncc_lib
+    if _wncc_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(WNCC_LIB_PATH):
+            raise RuntimeError(
+                f"{WNCC_LIB_PATH} is missing: the weighted NCC kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _wncc_lib = wncc_library(WNCC_LIB_PATH)
+    return _wncc_lib

@@ -419,7 +419,7 @@ class DRR(nn.Module):
 
     def ncc(self, fixed: torch.Tensor, rot: torch.Tensor, xyz: torch.Tensor, *,
             convention: str = "ZXY", degrees: bool = False, eps: float = 1e-5,
-            reduction: str = "none") -> torch.Tensor:
+            reduction: str = "none", weight: torch.Tensor = None) -> torch.Tensor:
         """Per-pose normalised cross-correlation of ``fixed`` ((1 | B), 1, H, W) with the DRRs at the
         Euler poses (rot, xyz) (B, 3): ``NormalizedCrossCorrelation2d(eps=eps)(fixed.expand(B, ...),
         self(rot, xyz, parameterization="euler_angles", convention=convention))`` -- the objective of
@@ -438,10 +438,16 @@ class DRR(nn.Module):
         registration step maximises.  On the fused route the sum comes out of the epilogue's own
         launch and its gradient goes back in as one value: ``loss.backward(gradient=one)`` with a
         ready-made ``one`` is a step without a reduction or a fill launch.  The per-pose values of
-        the call (detached, (B,)) are left in ``self.ncc_per_pose``."""
+        the call (detached, (B,)) are left in ``self.ncc_per_pose``.
+
+        ``weight`` ((1 | B), 1, H, W), >= 0 and finite: the weighted (masked) NCC of
+        include/diffdrr_wncc_hip.h -- pixels of weight 0 (collimator, dead pixels, instruments) are not read,
+        ``fixed`` may hold NaN there.  A float32 weight on the poses' device that takes no gradient keeps the
+        fused route (``renderers._EulerSiddonWnccFn``: two small fold launches more than without a weight);
+        anything else composes the same value from ``forward`` and the criterion with the weight."""
         from .metrics import NormalizedCrossCorrelation2d
         from .pose import _AXIS, _check_convention
-        from .renderers import _EulerSiddonNccFn
+        from .renderers import _EulerSiddonNccFn, _EulerSiddonWnccFn
 
         B = rot.shape[0]
         r, det = self.renderer, self.detector
@@ -459,6 +465,10 @@ class DRR(nn.Module):
               and torch.is_tensor(fixed) and fixed.dim() == 4 and fixed.shape[0] in (1, B)
               and fixed.shape[1:] == (1, det.height, det.width) and fixed.dtype == torch.float32
               and fixed.device == rot.device and not fixed.requires_grad and B > 0)
+        if ok and weight is not None:
+            ok = (torch.is_tensor(weight) and weight.dim() == 4 and weight.shape[0] in (1, B)
+                  and weight.shape[1:] == (1, det.height, det.width) and weight.dtype == torch.float32
+                  and weight.device == rot.device and not weight.requires_grad)
         if reduction not in ("none", "sum"):
             raise ValueError(f"reduction must be 'none' or 'sum', not {reduction}")
         if not ok:
@@ -467,7 +477,7 @@ class DRR(nn.Module):
                 # DRR(reshape=False) hands (B, C, N) back: the criterion wants the detector's grid,
                 # as the fused path reads it
                 img = img.view(B, -1, det.height, det.width)
-            vals = NormalizedCrossCorrelation2d(eps=eps)(fixed.expand(B, -1, -1, -1), img)
+            vals = NormalizedCrossCorrelation2d(eps=eps)(fixed.expand(B, -1, -1, -1), img, weight=weight)
             if reduction == "sum":
                 self.ncc_per_pose = vals.detach()
                 return vals.sum()
@@ -482,8 +492,13 @@ class DRR(nn.Module):
             else self._affine_inverse[:3, :]
         cfg = r._cfg(False, det=(det.height, det.width))
         x1 = fixed.reshape(fixed.shape[0], det.height * det.width)
-        res = _EulerSiddonNccFn.apply(rot, xyz, self.density, det._reorient[:3, :].contiguous(),
-                                      self._P_cache, Ainv, x1, axes, cfg, float(eps), reduction == "sum")
+        if weight is not None:
+            res = _EulerSiddonWnccFn.apply(rot, xyz, self.density, det._reorient[:3, :].contiguous(), self._P_cache,
+                                           Ainv, x1, weight.reshape(weight.shape[0], det.height * det.width), axes,
+                                           cfg, float(eps), reduction == "sum")
+        else:
+            res = _EulerSiddonNccFn.apply(rot, xyz, self.density, det._reorient[:3, :].contiguous(),
+                                          self._P_cache, Ainv, x1, axes, cfg, float(eps), reduction == "sum")
         if reduction == "sum":
             total, self.ncc_per_pose = res
             return total

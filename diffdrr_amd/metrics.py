@@ -67,6 +67,50 @@ class _PatchNCCFn(torch.autograd.Function):
         return g1, g2, None, None
 
 
+class _WeightedNCCFn(torch.autograd.Function):
+    """Whole-image NCC under per-pixel weights (include/diffdrr_wncc_hip.h: ddrr_wncc_forward /
+    ddrr_wncc_backward).  x1 (B or 1, N), x2 (B, N), w (B or 1, N) -> (B,); no gradient w.r.t. w."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w, eps):
+        out, stats = ops.wncc_forward(x1, x2, w, eps)
+        ctx.save_for_backward(x1, x2, w, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x1, x2, w, stats = ctx.saved_tensors
+        need1, need2 = ctx.needs_input_grad[:2]
+        if need1 and x1.shape[0] == 1 and x2.shape[0] != 1:
+            # (a fixed image shared by the batch: its gradient is a sum over the batch, as in _NCCFn)
+            g1, g2 = ops.wncc_backward(x1.expand_as(x2).contiguous(), x2, w, stats, g, True, need2)
+            return g1.sum(0, keepdim=True), g2, None, None
+        g1, g2 = ops.wncc_backward(x1, x2, w, stats, g, need1, need2)
+        return g1, g2, None, None
+
+
+def weighted_ncc(x1, x2, weight, eps=1e-5):
+    """The weighted NCC of include/diffdrr_wncc_hip.h as a torch composition: x1, x2 (B, C, H, W), weight
+    ((1 | B), 1, H, W) >= 0 -> (B,), the mean over the channels of
+        (sum_V w x1 x2 / Sw - mu1 mu2) / (s1 s2),  mu = sum_V w x / Sw,  s = sqrt(sum_V w (x - mu)^2 / Sw + eps),
+    V = {w != 0}: a pixel outside V is selected out (NaN there is safe), a channel with Sw <= 0 scores 0.
+    Differentiable in x1, x2 and the weight."""
+    on = weight != 0
+    w = torch.where(on, weight, torch.zeros_like(weight))
+    Sw = w.sum(dim=(-1, -2), keepdim=True)
+    some = Sw > 0
+    inv = torch.where(some, 1.0 / torch.where(some, Sw, torch.ones_like(Sw)), torch.zeros_like(Sw))
+
+    def centred(x):
+        x = torch.where(on, x, torch.zeros_like(x))
+        d = torch.where(on, x - (w * x).sum(dim=(-1, -2), keepdim=True) * inv, torch.zeros_like(x))
+        return d, ((w * d * d).sum(dim=(-1, -2), keepdim=True) * inv + eps).sqrt()
+
+    (d1, s1), (d2, s2) = centred(x1), centred(x2)
+    ncc = (w * d1 * d2).sum(dim=(-1, -2), keepdim=True) * inv / (s1 * s2)
+    return ncc.flatten(1).mean(dim=1)
+
+
 def to_patches(x, patch_size):
     """Every ``patch_size`` x ``patch_size`` window (stride 1) becomes one channel
     whose spatial extent is the window, so that :meth:`norm` z-scores each window
@@ -84,7 +128,13 @@ class NormalizedCrossCorrelation2d(torch.nn.Module):
         self.patch_size = patch_size
         self.eps = eps
 
-    def forward(self, x1, x2):
+    def forward(self, x1, x2, weight=None):
+        """``weight`` ((1 | B), 1, H, W), >= 0 and finite: the weighted (masked) NCC of
+        include/diffdrr_wncc_hip.h -- pixels with weight 0 are not read (NaN there is safe), the same weight
+        for every channel, the mean of the channels' values.  float32 images on the device and a weight that
+        takes no gradient go through the kernels, everything else through :func:`weighted_ncc`."""
+        if weight is not None:
+            return self._weighted(x1, x2, weight)
         if (self.patch_size is not None and not getattr(self, "_no_patch_kernel", False)
                 and x1.dim() == 4 and x1.shape == x2.shape and ops.on_device(x2)
                 and x1.device == x2.device and x1.dtype == x2.dtype == torch.float32
@@ -112,6 +162,28 @@ class NormalizedCrossCorrelation2d(torch.nn.Module):
             return _NCCFn.apply(a, x2.reshape(b, h * w), self.eps)
         score = (self.norm(x1) * self.norm(x2)).flatten(1).sum(1)
         return score / (c * h * w)
+
+    def _weighted(self, x1, x2, weight):
+        if self.patch_size is not None:
+            raise ValueError("a weight with patch_size is not supported: weighted windows are out of scope")
+        assert x1.shape == x2.shape, "Input images must be the same size"
+        b, c, h, w = x2.shape
+        if weight.dim() != 4 or weight.shape[0] not in (1, b) or tuple(weight.shape[1:]) != (1, h, w):
+            raise ValueError(f"weight has shape {tuple(weight.shape)}: (1 | {b}, 1, {h}, {w}) expected")
+        if (ops.on_device(x2) and x1.device == x2.device == weight.device
+                and x1.dtype == x2.dtype == weight.dtype == torch.float32
+                and b * c <= _lib.WNCC_MAX_POSES  # (pairs of one launch; beyond: the composition)
+                and not (torch.is_grad_enabled() and weight.requires_grad)):
+            shared = b > 1 and x1.stride(0) == 0 and c == 1
+            a = (x1[:1] if shared else x1).reshape(1 if shared else b * c, h * w)
+            # (one weight for the batch, given so or `expand`ed, is read in place; per-pose weights repeat per channel)
+            if weight.shape[0] == 1 or (b > 1 and weight.stride(0) == 0):
+                wt = weight[:1].reshape(1, h * w)
+            else:
+                wt = weight.expand(b, c, h, w).reshape(b * c, h * w)
+            val = _WeightedNCCFn.apply(a, x2.reshape(b * c, h * w), wt, self.eps)
+            return val.reshape(b, c).mean(dim=1) if c > 1 else val
+        return weighted_ncc(x1, x2, weight, self.eps)
 
     def norm(self, x):
         mu = x.mean(dim=[-1, -2], keepdim=True)
@@ -202,8 +274,10 @@ class GradientNormalizedCrossCorrelation2d(NormalizedCrossCorrelation2d):
         super().__init__(patch_size, **kwargs)
         self.sobel = Sobel(sigma)
 
-    def forward(self, x1, x2):
+    def forward(self, x1, x2, weight=None):
         g1, g2 = self.sobel(x1), self.sobel(x2)
+        if weight is not None:  # (the same weight for both Sobel channels, through the weighted kernels)
+            return self._weighted(g1, g2, weight)
         b, c, h, w = g2.shape
         if (self.patch_size is None and c == 2 and ops.on_device(g2) and g1.shape == g2.shape
                 and g2.dtype == torch.float32):
@@ -223,12 +297,14 @@ class MultiscaleNormalizedCrossCorrelation2d(torch.nn.Module):
         self.nccs = [NormalizedCrossCorrelation2d(p) for p in patch_sizes]
         self.patch_weights = patch_weights
 
-    def forward(self, x1, x2):
+    def forward(self, x1, x2, weight=None):
         # sum_i w_i ncc_i (reference metrics.py:58-63: the weighted scores stacked and summed) with one
         # launch per scale: the first scaled, the others added with their weight as `alpha`
+        if weight is not None and any(ncc.patch_size is not None for ncc in self.nccs):
+            raise ValueError("a weight applies to whole-image scales only: weighted windows are out of scope")
         total = None
         for w, ncc in zip(self.patch_weights, self.nccs):
-            v = ncc(x1, x2)
+            v = ncc(x1, x2) if weight is None else ncc(x1, x2, weight=weight)
             if total is None:
                 total = v * w
             elif isinstance(w, (int, float)):

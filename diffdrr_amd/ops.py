@@ -1792,6 +1792,120 @@ def lm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, dam
     return out
 
 
+# ------------------------------------------------- weighted (masked) NCC (libdiffdrr_wncc_hip.so)
+def _launch_wncc(name, device, *args):
+    """:func:`_launch` through the weighted NCC library."""
+    _launch_on(_lib.get_wncc_lib(), name, device, args)
+
+
+def _query_wncc(name, *args):
+    return _lib.get_wncc_lib().query(name, *args)
+
+
+_wncc_ws = {}  # (device, stream, B, N) -> workspace of ddrr_wncc_* (uninitialised: per-workgroup partials)
+
+
+def wncc_workspace(B, N, device):
+    """The per-workgroup partials of the weighted NCC entries for B pairs of N pixels (include/diffdrr_wncc_hip.h):
+    uninitialised, every call writes what it reads, so one buffer per (device, stream, B, N) serves every call on
+    that stream.  ``GraphedIteration`` creates it for its capture stream before it captures."""
+    dev = torch.device(device)
+    sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+    key = (dev, sid, int(B), int(N))
+    ws = _wncc_ws.get(key)
+    if ws is None:
+        n = int(_query_wncc("ddrr_wncc_workspace_bytes", int(B), int(N)))
+        ws = _wncc_ws[key] = torch.empty(n // 8, dtype=torch.float64, device=dev)
+    return ws
+
+
+def _weight_rows(name, w, B, N):
+    if w.dim() != 2 or w.shape[1] != N or w.shape[0] not in (1, B) or w.dtype != torch.float32:
+        raise ValueError(f"{name}: the weight has shape {tuple(w.shape)} {w.dtype}: float32 ({B}, {N}), or (1, {N}) "
+                         f"for one weight shared by the batch, expected")
+
+
+def _wncc_pair(name, x1, w, B, N):
+    """The checks and strides the four entries share -> (x1, x1_stride, w, w_stride)."""
+    _fixed_rows(name, x1, B, N)
+    _weight_rows(name, w, B, N)
+    if B > _lib.WNCC_MAX_POSES:
+        raise ValueError(f"{name}: at most {_lib.WNCC_MAX_POSES} pairs, got {B}")
+    return (x1.contiguous(), 0 if (x1.shape[0] == 1 and B != 1) else N,
+            w.contiguous(), 0 if (w.shape[0] == 1 and B != 1) else N)
+
+
+def wncc_forward(x1, x2, w, eps):
+    """Weighted NCC (include/diffdrr_wncc_hip.h) of x2 (B, N) with x1 ((B | 1), N) under the weights w ((B | 1), N),
+    >= 0 and finite; pixels with w == 0 are not read into any sum.  -> (ncc (B), stats (B, 6))"""
+    B, N = x2.shape
+    x1, s1, w, sw = _wncc_pair("wncc_forward", x1, w, B, N)
+    _require_gpu(x2)
+    x2 = x2.contiguous()
+    ncc = torch.empty(B, dtype=torch.float32, device=x2.device)
+    stats = torch.empty(B, _lib.WNCC_STATS, dtype=torch.float32, device=x2.device)
+    if B and N:
+        _launch_wncc("ddrr_wncc_forward", x2.device, x1.data_ptr(), s1, x2.data_ptr(), w.data_ptr(), sw, B, N,
+                     float(eps), wncc_workspace(B, N, x2.device).data_ptr(), ncc.data_ptr(), stats.data_ptr())
+    return ncc, stats
+
+
+def wncc_backward(x1, x2, w, stats, g_out, want_x1, want_x2):
+    """(g_x1 | None, g_x2 | None), each (B, N), of sum_b g_out[b] ncc_b; a shared x1 gets no gradient here."""
+    B, N = x2.shape
+    x1, s1, w, sw = _wncc_pair("wncc_backward", x1, w, B, N)
+    x2 = x2.contiguous()
+    g_out, g_stride = _batch_grad(g_out, B)
+    g_x2 = torch.empty_like(x2) if want_x2 else None
+    g_x1 = torch.empty_like(x2) if (want_x1 and s1 == N) else None
+    if B and N:
+        _launch_wncc("ddrr_wncc_backward", x2.device, x1.data_ptr(), s1, x2.data_ptr(), w.data_ptr(), sw,
+                     stats.data_ptr(), g_out.data_ptr(), g_stride, B, N, _ptr(g_x1), _ptr(g_x2))
+    return g_x1, g_x2
+
+
+def siddon_wncc_forward(aux, img, x1, w, eps, *, want_image=False, want_sum=False):
+    """:func:`siddon_ncc_forward` under per-pixel weights w ((B | 1), N): the image is formed from the blocked
+    record on the fly.  -> (ncc (B), stats (B, 6), image (B, N) | None[, sum of the B values (0-dim), with
+    ``want_sum``: added in pose order by the fold's own launch])"""
+    B, N = img.shape
+    _blocked_record_only("siddon_wncc_forward", aux, B, N)
+    x1, s1, w, sw = _wncc_pair("siddon_wncc_forward", x1, w, B, N)
+    img = img.contiguous()
+    dev = img.device
+    ncc = torch.empty(B, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, _lib.WNCC_STATS, dtype=torch.float32, device=dev)
+    out = torch.empty(B, N, dtype=torch.float32, device=dev) if want_image else None
+    total = (torch.empty((), dtype=torch.float32, device=dev) if B else
+             torch.zeros((), dtype=torch.float32, device=dev)) if want_sum else None
+    if B:
+        _launch_wncc("ddrr_wncc_siddon_forward", dev, aux.data_ptr(), img.data_ptr(), x1.data_ptr(), s1,
+                     w.data_ptr(), sw, B, N, float(eps), wncc_workspace(B, N, dev).data_ptr(), ncc.data_ptr(),
+                     stats.data_ptr(), _ptr(out), _ptr(total))
+    return (ncc, stats, out, total) if want_sum else (ncc, stats, out)
+
+
+def siddon_wncc_backward_pose(aux, x1, w, stats, g_out, source, Mw, Ainv, P, rot, xyz, axes, reorient34, *,
+                              eps=1e-8, with_img_path=True):
+    """(g_rot (B,3), g_xyz (B,3)) of sum_b g_out[b] ncc_b of :func:`siddon_wncc_forward`: the weighted NCC
+    backward, the record's ray gradients, the ray generation's adjoint and pose_euler_backward in two launches."""
+    B, N = rot.shape[0], P.shape[0]
+    _blocked_record_only("siddon_wncc_backward_pose", aux, B, N)
+    x1, s1, w, sw = _wncc_pair("siddon_wncc_backward_pose", x1, w, B, N)
+    g_out, g_stride = _batch_grad(g_out, B)
+    source, Mw, Ainv, P, rot, xyz, reorient34 = (t.contiguous() for t in (source, Mw, Ainv, P, rot, xyz, reorient34))
+    dev = rot.device
+    g_rot = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    g_xyz = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    if B:
+        _launch_wncc("ddrr_wncc_siddon_backward_pose", dev, aux.data_ptr(), x1.data_ptr(), s1, w.data_ptr(), sw,
+                     stats.data_ptr(), g_out.data_ptr(), g_stride, source.data_ptr(), Mw.data_ptr(), Ainv.data_ptr(),
+                     P.data_ptr(), rot.data_ptr(), xyz.data_ptr(), *axes, reorient34.data_ptr(), B, N, float(eps),
+                     int(bool(with_img_path)), wncc_workspace(B, N, dev).data_ptr(), g_rot.data_ptr(),
+                     g_xyz.data_ptr())
+    return g_rot, g_xyz
+
+
 # ------------------------------------------------- free-form deformation (libdiffdrr_warp_hip.so)
 _WARP_PADDING = {"zeros": _lib.WARP_PADDING_ZEROS, "border": _lib.WARP_PADDING_BORDER}
 

@@ -136,12 +136,17 @@ class GraphedIteration:
     and Euler pose parameters the iteration goes through ``DRR.ncc`` -- three fused launches around
     the brick kernel instead of nine -- where that applies (``self.fused_similarity`` says whether
     it was asked for; the value and the gradients are those of the criterion on the rendered
-    image, up to the order of the sums)."""
+    image, up to the order of the sums).
+
+    ``weight`` ((1 | B), 1, H, W), >= 0: the criterion's per-pixel weight (a mask of the collimator, of dead
+    pixels, of instruments the CT does not hold), read in place like ``target``.  The fused route passes it to
+    ``DRR.ncc``, the unfused one calls ``criterion(target, reg(), weight=weight)``."""
 
     def __init__(self, reg: Registration, criterion, optimizer, target: torch.Tensor,
                  warmup: int = 3, static_volume: bool = True, fused_similarity: bool = True,
-                 **render_kwargs):
+                 weight: torch.Tensor = None, **render_kwargs):
         self.reg, self.criterion, self.optimizer, self.target = reg, criterion, optimizer, target
+        self.weight = weight
         self.render_kwargs = render_kwargs
         self.iterations_done = 0
         for g in optimizer.param_groups:
@@ -173,7 +178,9 @@ class GraphedIteration:
             optimizer.zero_grad(set_to_none=True)
             if fused:
                 values = reg.drr.ncc(target, reg._rotation, reg._translation, convention=reg.convention,
-                                     eps=criterion.eps)
+                                     eps=criterion.eps, weight=weight)
+            elif weight is not None:
+                values = criterion(target, reg(**render_kwargs), weight=weight)
             else:
                 values = criterion(target, reg(**render_kwargs))
             loss = values.reshape(()) if values.numel() == 1 else values.sum()
@@ -195,10 +202,18 @@ class GraphedIteration:
             # stream -- exists before the capture: inside it, its zero-fill would become a node)
             cap = torch.cuda.Stream()
             cap.wait_stream(torch.cuda.current_stream())
-            if fused:
+            if fused or weight is not None:
                 from . import ops
+                from .metrics import GradientNormalizedCrossCorrelation2d
+                poses, pixels = reg._rotation.shape[0], target.shape[-2] * target.shape[-1]
                 with torch.cuda.stream(cap):
-                    ops.siddon_ncc_workspace(reg._rotation.shape[0], reg._rotation.device)
+                    if fused:
+                        ops.siddon_ncc_workspace(poses, reg._rotation.device)
+                    if weight is not None:
+                        # (the weighted kernels' partials, for the pairs either route launches: a pose's image, or
+                        # its two Sobel channels -- inside the capture the buffer would come from the graph's pool)
+                        channels = 2 if isinstance(criterion, GradientNormalizedCrossCorrelation2d) else 1
+                        ops.wncc_workspace(poses * channels, pixels, reg._rotation.device)
                 cap.synchronize()
             with torch.cuda.graph(self.graph, stream=cap):
                 self.loss = iteration()

@@ -582,6 +582,45 @@ class _EulerSiddonNccFn(torch.autograd.Function):
         return g_rot, g_xyz, None, None, None, None, None, None, None, None, None
 
 
+class _EulerSiddonWnccFn(torch.autograd.Function):
+    """``_EulerSiddonNccFn`` under per-pixel weights ((1 | B), N; no gradient w.r.t. them): the weighted (masked)
+    NCC of include/diffdrr_wncc_hip.h.  Forward: ddrr_pose_raygen_forward, the brick kernel with its record (no
+    image is written), ddrr_wncc_siddon_forward; backward: ddrr_wncc_siddon_backward_pose."""
+
+    @staticmethod
+    def forward(ctx, rot, xyz, volume, reorient34, P, Ainv, fixed, weight, axes, cfg, ncc_eps, reduce_sum=False):
+        B, N = rot.shape[0], P.shape[0]
+        aux = ops.brick_record_buffer(B, N, rot.device)
+        launch_ws = ops.launch_workspace(volume.shape, volume.device)
+        some = B > 0 and N > 0  # (an empty batch launches nothing)
+        Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, axes, reorient34, Ainv, P,
+                                                          clear=aux if some else None,
+                                                          clear_launch_ws=launch_ws if some else None)
+        ops.siddon_forward_bricks(
+            volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
+            want_aux=True, storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=False,
+            aux=aux, launch_ws=launch_ws, cleared=some)
+        ncc, stats, _, total = ops.siddon_wncc_forward(aux, img, fixed, weight, ncc_eps, want_sum=True) if reduce_sum \
+            else (*ops.siddon_wncc_forward(aux, img, fixed, weight, ncc_eps), None)
+        ctx.axes, ctx.cfg = axes, cfg
+        ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, fixed, weight, Mw, source, aux, stats)
+        if reduce_sum:  # (as _EulerSiddonNccFn: the sum differentiable, the per-pose values riding along)
+            ctx.mark_non_differentiable(ncc)
+            ctx.set_materialize_grads(False)
+            return total, ncc
+        return ncc
+
+    @staticmethod
+    def backward(ctx, g, _g_values=None):
+        if g is None:  # (reduce_sum with nothing flowing back)
+            return (None,) * 12
+        rot, xyz, reorient34, P, Ainv, fixed, weight, Mw, source, aux, stats = ctx.saved_tensors
+        g_rot, g_xyz = ops.siddon_wncc_backward_pose(
+            aux, fixed, weight, stats, g, source, Mw, Ainv, P, rot, xyz, ctx.axes, reorient34,
+            eps=ctx.cfg["eps"], with_img_path=not ctx.cfg["stop_gradients"])
+        return (g_rot, g_xyz) + (None,) * 10
+
+
 class _EulerSiddonImageFn(torch.autograd.Function):
     """``drr(rot, xyz, parameterization="euler_angles")`` for pose parameters that take a gradient, when the
     similarity is computed OUTSIDE the render (reference registration.py:32-42 with any criterion of
