@@ -456,9 +456,13 @@ def brick_fallbacks(volume, storage):
 def brick_storage_applies(volume) -> bool:
     """Whether the 16-bit brick storages can serve this volume tensor at all: a non-contiguous
     volume is a new temporary on every call (its workspace would be rebuilt -- and its memory
-    churned -- per render).  Any shape does (the reference's example CT has 133 slices: the
-    staging reads quads of four voxels from dword-aligned addresses)."""
-    return volume.dim() == 3 and volume.is_contiguous() and volume.numel() >= 4
+    churned -- per render).  Any shape of at least four slices does (the reference's example CT has
+    133: the staging reads quads of four voxels from dword-aligned addresses); a thinner volume is
+    rendered from its fp32 values by the general brick kernel whatever the storage
+    (csrc/bricks_fwd.hip launch_fwd_bricks, csrc/brick_core.h quads_serve), which builds no
+    workspace: handing it one would leave :func:`brick_fallbacks` and :func:`brick_workspace_stale`
+    reading words no launch has written."""
+    return volume.dim() == 3 and volume.is_contiguous() and volume.numel() >= 4 and volume.shape[2] >= 4
 
 
 def brick_ranges(volume):

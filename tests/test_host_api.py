@@ -998,8 +998,9 @@ def test_trilinear_channels_on_bricks_on_the_host(emulated_ops):
 @pytest.mark.parametrize("dims", [(70, 50, 133), (33, 34, 5), (20, 24, 3), (40, 36, 1), (3, 50, 1), (2, 3, 37)])
 def test_any_depth_on_every_brick_storage_on_the_host(emulated_ops, dims):
     """The host twin of tests/test_gpu_brick_storage.py::test_any_depth_on_the_configurable_kernel:
-    the Python layer hands volumes of any D.z to the 16-bit storages (ops.brick_storage_applies)
-    and the emulation of the same entry points agrees with the per-ray walk."""
+    the Python layer hands volumes of any D.z >= 4 to the 16-bit storages and thinner ones to the fp32
+    bricks, as the device's launcher does (ops.brick_storage_applies), and the emulation of the same
+    entry points agrees with the per-ray walk."""
     import test_gpu_brick_storage as G
 
     G.test_any_depth_on_the_configurable_kernel("cpu", dims)
