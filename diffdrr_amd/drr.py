@@ -19,8 +19,10 @@ from torch.utils.checkpoint import checkpoint
 
 from . import ops
 from .detector import Detector
-from .pose import RigidTransform, convert, euler_world_pose
-from .renderers import Siddon, Trilinear
+from .metrics import NormalizedCrossCorrelation2d
+from .pose import _AXIS, RigidTransform, _check_convention, convert, euler_world_pose
+from .renderers import (Siddon, Trilinear, _euler_siddon_render, _EulerSiddonImageFn, _EulerSiddonNccFn,
+                        _EulerSiddonWnccFn)
 
 
 class DRR(nn.Module):
@@ -101,6 +103,12 @@ class DRR(nn.Module):
     @property
     def affine_inverse(self):
         return RigidTransform(self._affine_inverse)
+
+    @property
+    def _affine_inverse34(self):
+        """(3, 4) world -> voxel: the rows of the inverse affine the kernels take."""
+        A = self._affine_inverse
+        return A[0, :3, :] if A.dim() == 3 else A[:3, :]
 
     @property
     def n_patches(self):
@@ -236,8 +244,7 @@ class DRR(nn.Module):
     def _render_fused_Mw(self, Mw, calibration, mask_to_channels=False, **kwargs):
         det = self.detector
         P = self._calibrated_points(calibration)
-        Ainv = self._affine_inverse[0, :3, :] if self._affine_inverse.dim() == 3 \
-            else self._affine_inverse[:3, :]
+        Ainv = self._affine_inverse34
         if self.patch_size is not None or det.n_subsample is not None:
             return self._render_sparse(Mw, P, Ainv, self.mask if mask_to_channels else None, **kwargs)
         # the grid contract holds for THIS call only (rays generated right here): a later direct
@@ -347,41 +354,38 @@ class DRR(nn.Module):
             outs.append(out if local is None else out.index_select(-1, local))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=-1)
 
+    def _euler_bricks_ok(self, rot, xyz):
+        """What every fused Euler-pose route asks for (``_render_euler_inference``, ``_render_euler_differentiable``,
+        ``ncc``; ``LevenbergMarquardt`` refuses the same one by one): a Siddon render on the bricks with the float
+        record, a batch that is not empty, one shape for both parameters, everything on the volume's device.  Each
+        route adds what is its own."""
+        r = self.renderer
+        return (isinstance(r, Siddon) and r.grid_path == "bricks" and not r.packed_record and rot.shape[0] > 0
+                and rot.shape == xyz.shape and rot.device == self.density.device == xyz.device)
+
+    def _euler_args(self, rot, convention, degrees):
+        """(rot, convention, degrees) -> what ``renderers._euler_siddon_render`` takes behind (rot, xyz, volume):
+        (rot in radians, reorient34, P, Ainv, axes, cfg)."""
+        _check_convention(convention)
+        if degrees:
+            rot = rot / 180 * math.pi
+        det = self.detector
+        return (rot, det._reorient[:3, :].contiguous(), self._calibrated_points(), self._affine_inverse34,
+                tuple(_AXIS[c] for c in convention), self.renderer._cfg(False, det=(det.height, det.width)))
+
     def _render_euler_inference(self, rot, xyz, convention, degrees):
         """The everyday call -- ``drr(rot, xyz, parameterization="euler_angles")`` with nothing to
         differentiate -- in TWO launches: pose -> matrix -> rays (which also clears the image and
         the brick counter of the render behind it), and the brick kernel.  The same kernels'
         arithmetic as the differentiable path (four launches: pose, rays, clear, render); None
         where that path does not apply (then the caller takes the usual one)."""
-        from .pose import _AXIS, _check_convention
-        from .renderers import _brick_axis, _brick_storage
-
-        r, det = self.renderer, self.detector
-        B = rot.shape[0]
-        if not (isinstance(r, Siddon) and r.grid_path == "bricks" and not r.packed_record and B > 0
-                and rot.shape == xyz.shape and rot.device == self.density.device == xyz.device):
+        if not self._euler_bricks_ok(rot, xyz):
             return None
-        _check_convention(convention)
-        if degrees:
-            rot = rot / 180 * math.pi
-        axes = tuple(_AXIS[c] for c in convention)
-        P = self._calibrated_points()
-        Ainv = self._affine_inverse[0, :3, :] if self._affine_inverse.dim() == 3 \
-            else self._affine_inverse[:3, :]
-        cfg = r._cfg(False, det=(det.height, det.width))
+        rot, *args = self._euler_args(rot, convention, degrees)
         with torch.no_grad():
-            out = torch.empty(B, P.shape[0], dtype=torch.float32, device=rot.device)
-            launch_ws = ops.launch_workspace(self.density.shape, self.density.device)
-            _, source, target, img = ops.pose_raygen_forward(
-                rot.detach(), xyz.detach(), axes, det._reorient[:3, :].contiguous(), Ainv, P, clear=out,
-                clear_launch_ws=launch_ws)
-            # (the density tensor itself: its packed bricks are cached per tensor object and version)
-            ops.siddon_forward_bricks(self.density, source, target, img, cfg["det"],
-                                      voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-                                      storage=_brick_storage(self.density, cfg, B),
-                                      axis=_brick_axis(self.density, cfg, B), out=out, launch_ws=launch_ws,
-                                      cleared=True, pixel_mask=det.subsample_mask())
-        if det.n_subsample is not None:  # (p_subsample: the scattered grid, see _reshape_fused)
+            out = _euler_siddon_render(rot.detach(), xyz.detach(), self.density, *args, record=False,
+                                       pixel_mask=self.detector.subsample_mask())[-1]
+        if self.detector.n_subsample is not None:  # (p_subsample: the scattered grid, see _reshape_fused)
             return _ScatteredGrid(out.unsqueeze(1))
         return out.unsqueeze(1)
 
@@ -392,28 +396,13 @@ class DRR(nn.Module):
         composition of ``euler_world_pose`` and ``render_poses`` takes five and three.  None where that
         does not apply -- a dense Siddon render on the bricks of a volume that takes no gradient, at most
         ``FUSED_NCC_MAX_POSES`` poses (beyond, the launches are bound by their bytes, not their count)."""
-        from .pose import _AXIS, _check_convention
-        from .renderers import _EulerSiddonImageFn
-
-        r, det = self.renderer, self.detector
-        B = rot.shape[0]
         if not (torch.is_grad_enabled() and (rot.requires_grad or xyz.requires_grad)
-                and not self.density.requires_grad and isinstance(r, Siddon) and r.grid_path == "bricks"
-                and not r.packed_record and 0 < B <= self.FUSED_NCC_MAX_POSES and rot.shape == xyz.shape
-                and rot.device == self.density.device == xyz.device
-                and self.patch_size is None and det.n_subsample is None and self.fuse_ray_generation):
+                and not self.density.requires_grad and self._euler_bricks_ok(rot, xyz)
+                and rot.shape[0] <= self.FUSED_NCC_MAX_POSES and self.patch_size is None
+                and self.detector.n_subsample is None and self.fuse_ray_generation):
             return None
-        _check_convention(convention)
-        if degrees:
-            rot = rot / 180 * math.pi
-        axes = tuple(_AXIS[c] for c in convention)
-        P = self._calibrated_points()
-        Ainv = self._affine_inverse[0, :3, :] if self._affine_inverse.dim() == 3 \
-            else self._affine_inverse[:3, :]
-        cfg = r._cfg(False, det=(det.height, det.width))
-        out = _EulerSiddonImageFn.apply(rot, xyz, self.density, det._reorient[:3, :].contiguous(), P, Ainv,
-                                        axes, cfg)
-        return out.unsqueeze(1)
+        rot, *args = self._euler_args(rot, convention, degrees)
+        return _EulerSiddonImageFn.apply(rot, xyz, self.density, *args).unsqueeze(1)
 
     FUSED_NCC_MAX_POSES = 32
 
@@ -445,12 +434,8 @@ class DRR(nn.Module):
         ``fixed`` may hold NaN there.  A float32 weight on the poses' device that takes no gradient keeps the
         fused route (``renderers._EulerSiddonWnccFn``: two small fold launches more than without a weight);
         anything else composes the same value from ``forward`` and the criterion with the weight."""
-        from .metrics import NormalizedCrossCorrelation2d
-        from .pose import _AXIS, _check_convention
-        from .renderers import _EulerSiddonNccFn, _EulerSiddonWnccFn
-
         B = rot.shape[0]
-        r, det = self.renderer, self.detector
+        det = self.detector
         # (at most FUSED_NCC_MAX_POSES poses: the launches around the brick kernel are bound by their
         # bytes, not by their count, from a few dozen poses on -- 16 poses 0.821 against 0.875 ms per
         # eager step; 32 poses 1.481 against 1.488 at 512^3, 0.721 against 0.751 at 256^3 since the
@@ -458,13 +443,13 @@ class DRR(nn.Module):
         # not measured beyond: profiles/r05/fused_step.txt)
         ok = (torch.is_grad_enabled() and (rot.requires_grad or xyz.requires_grad)
               and B <= self.FUSED_NCC_MAX_POSES
-              and self._fused_ok(False, {}, None, dense_only=True) and isinstance(r, Siddon)
-              and r.grid_path == "bricks" and not r.packed_record and not self.density.requires_grad
+              and self._fused_ok(False, {}, None, dense_only=True) and not self.density.requires_grad
               and all(torch.is_tensor(a) and a.dim() == 2 and a.shape == (B, 3)
                       and a.dtype == torch.float32 and ops.on_device(a) for a in (rot, xyz))
+              and self._euler_bricks_ok(rot, xyz)
               and torch.is_tensor(fixed) and fixed.dim() == 4 and fixed.shape[0] in (1, B)
               and fixed.shape[1:] == (1, det.height, det.width) and fixed.dtype == torch.float32
-              and fixed.device == rot.device and not fixed.requires_grad and B > 0)
+              and fixed.device == rot.device and not fixed.requires_grad)
         if ok and weight is not None:
             ok = (torch.is_tensor(weight) and weight.dim() == 4 and weight.shape[0] in (1, B)
                   and weight.shape[1:] == (1, det.height, det.width) and weight.dtype == torch.float32
@@ -482,23 +467,12 @@ class DRR(nn.Module):
                 self.ncc_per_pose = vals.detach()
                 return vals.sum()
             return vals
-        _check_convention(convention)
-        if degrees:
-            rot = rot / 180 * math.pi
-        axes = tuple(_AXIS[c] for c in convention)
-        # (as _render_fused_Mw: the calibrated detector points, cached per intrinsics)
-        self._calibrated_points()
-        Ainv = self._affine_inverse[0, :3, :] if self._affine_inverse.dim() == 3 \
-            else self._affine_inverse[:3, :]
-        cfg = r._cfg(False, det=(det.height, det.width))
-        x1 = fixed.reshape(fixed.shape[0], det.height * det.width)
-        if weight is not None:
-            res = _EulerSiddonWnccFn.apply(rot, xyz, self.density, det._reorient[:3, :].contiguous(), self._P_cache,
-                                           Ainv, x1, weight.reshape(weight.shape[0], det.height * det.width), axes,
-                                           cfg, float(eps), reduction == "sum")
-        else:
-            res = _EulerSiddonNccFn.apply(rot, xyz, self.density, det._reorient[:3, :].contiguous(),
-                                          self._P_cache, Ainv, x1, axes, cfg, float(eps), reduction == "sum")
+        rot, *args = self._euler_args(rot, convention, degrees)
+        N = det.height * det.width
+        # (one body under two names: the node of a weighted step is ``_EulerSiddonWnccFn``)
+        res = (_EulerSiddonNccFn if weight is None else _EulerSiddonWnccFn).apply(
+            rot, xyz, self.density, *args, fixed.reshape(fixed.shape[0], N),
+            None if weight is None else weight.reshape(weight.shape[0], N), float(eps), reduction == "sum")
         if reduction == "sum":
             total, self.ncc_per_pose = res
             return total

@@ -764,6 +764,19 @@ def _fixed_rows(name, x1, B, N):
                          f"by the batch, expected")
 
 
+def _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34):
+    """The pose chain as the entries behind :func:`pose_raygen_forward` take it -> (the contiguous tensors, for the
+    caller to hold until its launch; the argument run ``Mw, Ainv, P, rot, xyz, *axes, reorient34``)."""
+    Mw, Ainv, P, rot, xyz, reorient34 = held = tuple(t.contiguous() for t in (Mw, Ainv, P, rot, xyz, reorient34))
+    return held, (Mw.data_ptr(), Ainv.data_ptr(), P.data_ptr(), rot.data_ptr(), xyz.data_ptr(), *axes,
+                  reorient34.data_ptr())
+
+
+def _pose_grads(B, device):
+    """(g_rot, g_xyz): two (B, 3) float32 tensors for an entry to write."""
+    return torch.empty(B, 3, dtype=torch.float32, device=device), torch.empty(B, 3, dtype=torch.float32, device=device)
+
+
 def siddon_ncc_workspace(B, device):
     """The caller-owned accumulators / tickets of :func:`siddon_ncc_forward` and
     :func:`siddon_ncc_backward_pose`: zero when first handed over, left zero by every call, so one
@@ -856,17 +869,14 @@ def siddon_ncc_backward_pose(aux, img, x1, stats, g_out, source, target, Mw, Ain
     shared = x1.shape[0] == 1 and B != 1
     g_out, g_stride = _batch_grad(g_out, B)
     x1, img, source, target = (t.contiguous() for t in (x1, img, source, target))
-    Mw, Ainv, P, rot, xyz, reorient34 = (t.contiguous() for t in (Mw, Ainv, P, rot, xyz, reorient34))
+    held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
     dev = img.device
-    g_rot = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    g_xyz = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    g_rot, g_xyz = _pose_grads(B, dev)
     if B:
         _launch("ddrr_siddon_ncc_backward_pose", dev, aux.data_ptr(), img.data_ptr(), x1.data_ptr(),
                 0 if shared else N, stats.data_ptr(), g_out.data_ptr(), g_stride, source.data_ptr(),
-                target.data_ptr(), Mw.data_ptr(), Ainv.data_ptr(), P.data_ptr(), rot.data_ptr(),
-                xyz.data_ptr(), *axes, reorient34.data_ptr(), B, N, float(eps),
-                int(bool(with_img_path)), siddon_ncc_workspace(B, dev).data_ptr(), g_rot.data_ptr(),
-                g_xyz.data_ptr())
+                target.data_ptr(), *chain, B, N, float(eps), int(bool(with_img_path)),
+                siddon_ncc_workspace(B, dev).data_ptr(), g_rot.data_ptr(), g_xyz.data_ptr())
     return g_rot, g_xyz
 
 
@@ -877,15 +887,13 @@ def siddon_backward_pose_euler(aux, grad_out, source, Mw, Ainv, P, rot, xyz, axe
     B, N = grad_out.shape
     _blocked_record_only("siddon_backward_pose_euler", aux, B, N)
     grad_out, source = grad_out.contiguous(), source.contiguous()
-    Mw, Ainv, P, rot, xyz, reorient34 = (t.contiguous() for t in (Mw, Ainv, P, rot, xyz, reorient34))
+    held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
     dev = grad_out.device
-    g_rot = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    g_xyz = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    g_rot, g_xyz = _pose_grads(B, dev)
     if B:
         _launch("ddrr_siddon_backward_pose_euler", dev, aux.data_ptr(), grad_out.data_ptr(), source.data_ptr(),
-                Mw.data_ptr(), Ainv.data_ptr(), P.data_ptr(), rot.data_ptr(), xyz.data_ptr(), *axes,
-                reorient34.data_ptr(), B, N, float(eps), int(bool(with_img_path)),
-                siddon_ncc_workspace(B, dev).data_ptr(), g_rot.data_ptr(), g_xyz.data_ptr())
+                *chain, B, N, float(eps), int(bool(with_img_path)), siddon_ncc_workspace(B, dev).data_ptr(),
+                g_rot.data_ptr(), g_xyz.data_ptr())
     return g_rot, g_xyz
 
 
@@ -1755,8 +1763,8 @@ def lm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient34, 
     if B > _lib.LM_MAX_POSES:
         raise ValueError(f"lm_normal_sums: at most {_lib.LM_MAX_POSES} poses, got {B}")
     shared = fixed.shape[0] == 1 and B != 1
-    fixed, source, Mw, Ainv, P, rot, xyz, reorient34 = (
-        t.contiguous() for t in (fixed, source, Mw, Ainv, P, rot, xyz, reorient34))
+    fixed, source = fixed.contiguous(), source.contiguous()
+    held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
     dev = rot.device
     if ws is None:
         ws = lm_workspace(B, N, dev)
@@ -1765,9 +1773,7 @@ def lm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient34, 
     jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
     if B and N:
         _launch_lm("ddrr_lm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), 0 if shared else N,
-                   source.data_ptr(), Mw.data_ptr(), Ainv.data_ptr(), P.data_ptr(), rot.data_ptr(), xyz.data_ptr(),
-                   *axes, reorient34.data_ptr(), B, N, float(eps), int(bool(with_img_path)), ws.data_ptr(),
-                   _ptr(jac))
+                   source.data_ptr(), *chain, B, N, float(eps), int(bool(with_img_path)), ws.data_ptr(), _ptr(jac))
     return ws, jac
 
 
@@ -1897,14 +1903,13 @@ def siddon_wncc_backward_pose(aux, x1, w, stats, g_out, source, Mw, Ainv, P, rot
     _blocked_record_only("siddon_wncc_backward_pose", aux, B, N)
     x1, s1, w, sw = _wncc_pair("siddon_wncc_backward_pose", x1, w, B, N)
     g_out, g_stride = _batch_grad(g_out, B)
-    source, Mw, Ainv, P, rot, xyz, reorient34 = (t.contiguous() for t in (source, Mw, Ainv, P, rot, xyz, reorient34))
+    source = source.contiguous()
+    held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
     dev = rot.device
-    g_rot = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    g_xyz = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    g_rot, g_xyz = _pose_grads(B, dev)
     if B:
         _launch_wncc("ddrr_wncc_siddon_backward_pose", dev, aux.data_ptr(), x1.data_ptr(), s1, w.data_ptr(), sw,
-                     stats.data_ptr(), g_out.data_ptr(), g_stride, source.data_ptr(), Mw.data_ptr(), Ainv.data_ptr(),
-                     P.data_ptr(), rot.data_ptr(), xyz.data_ptr(), *axes, reorient34.data_ptr(), B, N, float(eps),
+                     stats.data_ptr(), g_out.data_ptr(), g_stride, source.data_ptr(), *chain, B, N, float(eps),
                      int(bool(with_img_path)), wncc_workspace(B, N, dev).data_ptr(), g_rot.data_ptr(),
                      g_xyz.data_ptr())
     return g_rot, g_xyz

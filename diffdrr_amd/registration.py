@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from .pose import convert
+from .renderers import _euler_siddon_render
 
 
 class Registration(nn.Module):
@@ -306,7 +307,7 @@ class LevenbergMarquardt:
                  down: float = 1.0 / 3.0, damping_min: float = 1e-7, damping_max: float = 1e6, eps: float = 1e-5,
                  graph: bool = False):
         from . import ops
-        from .pose import _AXIS, _check_convention
+        from .pose import _check_convention
         from .renderers import Siddon
 
         if graph:
@@ -360,7 +361,6 @@ class LevenbergMarquardt:
         if fixed.device != rot.device:
             refuse(f"fixed must live on the parameters' device ({rot.device}), got {fixed.device}")
         self.B, self.N = B, H * W
-        self.axes = tuple(_AXIS[c] for c in reg.convention)
         self.fixed = fixed.detach().reshape(fixed.shape[0], H * W).contiguous()
         dev = rot.device
         self._state = ops.lm_state(B, damping, dev)
@@ -371,24 +371,12 @@ class LevenbergMarquardt:
 
     # -- one render of the current parameters with its record: the first two launches of a step
     def _render(self):
-        from . import ops
-        from .renderers import _brick_axis, _brick_storage
-
-        drr, reg = self.reg.drr, self.reg
-        r, det = drr.renderer, drr.detector
-        P = drr._calibrated_points()
-        Ainv = drr._affine_inverse[0, :3, :] if drr._affine_inverse.dim() == 3 else drr._affine_inverse[:3, :]
-        cfg = r._cfg(False, det=(det.height, det.width))
-        reorient34 = det._reorient[:3, :].contiguous()
-        rot, xyz = reg._rotation.detach(), reg._translation.detach()
-        launch_ws = ops.launch_workspace(drr.density.shape, drr.density.device)
-        Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, self.axes, reorient34, Ainv, P, clear=self._aux,
-                                                          clear_launch_ws=launch_ws)
-        ops.siddon_forward_bricks(drr.density, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"],
-                                  eps=cfg["eps"], want_aux=True, storage=_brick_storage(drr.density, cfg, self.B),
-                                  axis=_brick_axis(drr.density, cfg, self.B),
-                                  want_image=False, aux=self._aux, launch_ws=launch_ws, cleared=True)
-        return dict(aux=self._aux, source=source, Mw=Mw, Ainv=Ainv, P=P, rot=rot, xyz=xyz, axes=self.axes,
+        drr = self.reg.drr
+        rot, xyz = self.reg._rotation.detach(), self.reg._translation.detach()
+        rot, reorient34, P, Ainv, axes, cfg = drr._euler_args(rot, self.reg.convention, False)
+        Mw, source, _, _, aux, _ = _euler_siddon_render(rot, xyz, drr.density, reorient34, P, Ainv, axes, cfg,
+                                                        aux=self._aux)
+        return dict(aux=aux, source=source, Mw=Mw, Ainv=Ainv, P=P, rot=rot, xyz=xyz, axes=axes,
                     reorient34=reorient34), dict(eps=cfg["eps"], with_img_path=not cfg["stop_gradients"])
 
     @torch.no_grad()

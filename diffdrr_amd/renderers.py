@@ -532,115 +532,98 @@ def _pixel_mask_bits(pixel_mask, n_pixels):
     return ((pixel_mask.unsqueeze(-1) >> shifts) & 1).view(-1)[:n_pixels].bool()
 
 
+def _euler_siddon_render(rot, xyz, volume, reorient34, P, Ainv, axes, cfg, *, record=True, aux=None,
+                         want_image=False, pixel_mask=None):
+    """The two launches every fused Euler-pose route starts with: ddrr_pose_raygen_forward (pose -> matrix -> rays,
+    and the clears of the render behind it) and the brick kernel -- the one place that knows their order and the
+    ``clear`` / ``cleared`` / ``launch_ws`` contract between them.  Arguments as ``DRR._euler_args`` makes them.
+    ``record``: the render writes its blocked float record (into ``aux`` where the caller keeps one), and with
+    ``want_image`` the image formed from it; without a record the image alone, of the pixels in ``pixel_mask`` where
+    one is given.  What the brick kernel's atomics add to -- the record, else the image -- and the launch workspace
+    are cleared by the first launch; an empty batch clears and launches nothing.
+    -> (Mw, source, target, img, aux | None, image | None)"""
+    B, N = rot.shape[0], P.shape[0]
+    if record and aux is None:
+        aux = ops.brick_record_buffer(B, N, rot.device)
+    out = None if record else torch.empty(B, N, dtype=torch.float32, device=rot.device)
+    launch_ws = ops.launch_workspace(volume.shape, volume.device)
+    some = B > 0 and N > 0  # (an empty batch launches nothing)
+    Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, axes, reorient34, Ainv, P,
+                                                      clear=(aux if record else out) if some else None,
+                                                      clear_launch_ws=launch_ws if some else None)
+    # (the volume tensor itself: its packed bricks are cached per tensor object and version)
+    out, _ = ops.siddon_forward_bricks(
+        volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"], want_aux=record,
+        storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=want_image or not record,
+        aux=aux, out=out, launch_ws=launch_ws, cleared=some, pixel_mask=pixel_mask)
+    return Mw, source, target, img, aux, out
+
+
 class _EulerSiddonNccFn(torch.autograd.Function):
     """A registration step's forward and backward around the brick kernel in three launches
     instead of nine: (rot, xyz) Euler pose parameters -> per-pose NCC of the DRR with a fixed
-    image.  Forward: ddrr_pose_raygen_forward (pose -> matrix -> rays), the brick kernel with its
-    record (no image is written), ddrr_siddon_ncc_forward (image from the record + NCC).
-    Backward: ddrr_siddon_ncc_backward_pose (NCC backward, the record's ray gradients chained
+    image.  Forward: ``_euler_siddon_render`` with the record and no image, ddrr_siddon_ncc_forward (image from the
+    record + NCC).  Backward: ddrr_siddon_ncc_backward_pose (NCC backward, the record's ray gradients chained
     through the ray generation, matrix -> pose parameters).  The arithmetic per element is that
     of ``NormalizedCrossCorrelation2d()(fixed, drr(rot, xyz, parameterization="euler_angles"))``
-    (reference registration.py:32-42, metrics.py:21-44); only the order of the sums differs."""
+    (reference registration.py:32-42, metrics.py:21-44); only the order of the sums differs.
+    With ``weight`` ((1 | B), N; no gradient w.r.t. it): the weighted (masked) NCC of include/diffdrr_wncc_hip.h
+    -- the same step around ddrr_wncc_siddon_forward | ddrr_wncc_siddon_backward_pose, under the name
+    ``_EulerSiddonWnccFn``."""
 
     @staticmethod
-    def forward(ctx, rot, xyz, volume, reorient34, P, Ainv, fixed, axes, cfg, ncc_eps, reduce_sum=False):
-        # (the record and the brick counter of the render are cleared by the launch in front of it)
-        B, N = rot.shape[0], P.shape[0]
-        aux = ops.brick_record_buffer(B, N, rot.device)
-        launch_ws = ops.launch_workspace(volume.shape, volume.device)
-        some = B > 0 and N > 0  # (an empty batch launches nothing)
-        Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, axes, reorient34, Ainv, P,
-                                                          clear=aux if some else None,
-                                                          clear_launch_ws=launch_ws if some else None)
-        ops.siddon_forward_bricks(
-            volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-            want_aux=True, storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=False, aux=aux,
-            launch_ws=launch_ws, cleared=some)
-        ncc, stats, _, total = ops.siddon_ncc_forward(aux, img, fixed, ncc_eps, want_sum=True) if reduce_sum \
-            else (*ops.siddon_ncc_forward(aux, img, fixed, ncc_eps), None)
-        ctx.axes, ctx.cfg = axes, cfg
-        ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, fixed, Mw, source, target, img, aux, stats)
+    def forward(ctx, rot, xyz, volume, reorient34, P, Ainv, axes, cfg, fixed, weight, ncc_eps, reduce_sum=False):
+        Mw, source, target, img, aux, _ = _euler_siddon_render(rot, xyz, volume, reorient34, P, Ainv, axes, cfg)
+        if weight is None:
+            ncc, stats, _, *total = ops.siddon_ncc_forward(aux, img, fixed, ncc_eps, want_sum=reduce_sum)
+            ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, Mw, source, aux, stats, fixed, target, img)
+        else:
+            ncc, stats, _, *total = ops.siddon_wncc_forward(aux, img, fixed, weight, ncc_eps, want_sum=reduce_sum)
+            ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, Mw, source, aux, stats, fixed, weight)
+        ctx.axes, ctx.cfg, ctx.weighted = axes, cfg, weight is not None
+        if not reduce_sum:
+            return ncc
         # (reduce_sum: the batch's objective sum_b ncc_b, put together by the epilogue's own launch; its
         # gradient arrives as ONE value, which the backward epilogue reads with stride 0; the per-pose
-        # values ride along, not differentiable)
-        if reduce_sum:
-            # (the per-pose values take no gradient -- and autograd is not to fill one with zeros
-            # for them: one launch per step)
-            ctx.mark_non_differentiable(ncc)
-            ctx.set_materialize_grads(False)
-            return total, ncc
-        return ncc
-
-    @staticmethod
-    def backward(ctx, g, _g_values=None):
-        if g is None:  # (reduce_sum with nothing flowing back)
-            return (None,) * 11
-        rot, xyz, reorient34, P, Ainv, fixed, Mw, source, target, img, aux, stats = ctx.saved_tensors
-        g_rot, g_xyz = ops.siddon_ncc_backward_pose(
-            aux, img, fixed, stats, g, source, target, Mw, Ainv, P, rot, xyz, ctx.axes, reorient34,
-            eps=ctx.cfg["eps"], with_img_path=not ctx.cfg["stop_gradients"])
-        return g_rot, g_xyz, None, None, None, None, None, None, None, None, None
-
-
-class _EulerSiddonWnccFn(torch.autograd.Function):
-    """``_EulerSiddonNccFn`` under per-pixel weights ((1 | B), N; no gradient w.r.t. them): the weighted (masked)
-    NCC of include/diffdrr_wncc_hip.h.  Forward: ddrr_pose_raygen_forward, the brick kernel with its record (no
-    image is written), ddrr_wncc_siddon_forward; backward: ddrr_wncc_siddon_backward_pose."""
-
-    @staticmethod
-    def forward(ctx, rot, xyz, volume, reorient34, P, Ainv, fixed, weight, axes, cfg, ncc_eps, reduce_sum=False):
-        B, N = rot.shape[0], P.shape[0]
-        aux = ops.brick_record_buffer(B, N, rot.device)
-        launch_ws = ops.launch_workspace(volume.shape, volume.device)
-        some = B > 0 and N > 0  # (an empty batch launches nothing)
-        Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, axes, reorient34, Ainv, P,
-                                                          clear=aux if some else None,
-                                                          clear_launch_ws=launch_ws if some else None)
-        ops.siddon_forward_bricks(
-            volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-            want_aux=True, storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=False,
-            aux=aux, launch_ws=launch_ws, cleared=some)
-        ncc, stats, _, total = ops.siddon_wncc_forward(aux, img, fixed, weight, ncc_eps, want_sum=True) if reduce_sum \
-            else (*ops.siddon_wncc_forward(aux, img, fixed, weight, ncc_eps), None)
-        ctx.axes, ctx.cfg = axes, cfg
-        ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, fixed, weight, Mw, source, aux, stats)
-        if reduce_sum:  # (as _EulerSiddonNccFn: the sum differentiable, the per-pose values riding along)
-            ctx.mark_non_differentiable(ncc)
-            ctx.set_materialize_grads(False)
-            return total, ncc
-        return ncc
+        # values ride along: they take no gradient -- and autograd is not to fill one with zeros for
+        # them: one launch per step)
+        ctx.mark_non_differentiable(ncc)
+        ctx.set_materialize_grads(False)
+        return total[0], ncc
 
     @staticmethod
     def backward(ctx, g, _g_values=None):
         if g is None:  # (reduce_sum with nothing flowing back)
             return (None,) * 12
-        rot, xyz, reorient34, P, Ainv, fixed, weight, Mw, source, aux, stats = ctx.saved_tensors
-        g_rot, g_xyz = ops.siddon_wncc_backward_pose(
-            aux, fixed, weight, stats, g, source, Mw, Ainv, P, rot, xyz, ctx.axes, reorient34,
-            eps=ctx.cfg["eps"], with_img_path=not ctx.cfg["stop_gradients"])
-        return (g_rot, g_xyz) + (None,) * 10
+        rot, xyz, reorient34, P, Ainv, Mw, source, aux, stats, fixed, *rest = ctx.saved_tensors
+        chain = (Mw, Ainv, P, rot, xyz, ctx.axes, reorient34)
+        eps, with_img_path = ctx.cfg["eps"], not ctx.cfg["stop_gradients"]
+        if ctx.weighted:
+            grads = ops.siddon_wncc_backward_pose(aux, fixed, rest[0], stats, g, source, *chain, eps=eps,
+                                                  with_img_path=with_img_path)
+        else:
+            target, img = rest
+            grads = ops.siddon_ncc_backward_pose(aux, img, fixed, stats, g, source, target, *chain, eps=eps,
+                                                 with_img_path=with_img_path)
+        return grads + (None,) * 10
+
+
+class _EulerSiddonWnccFn(_EulerSiddonNccFn):
+    """``_EulerSiddonNccFn`` called with a weight: a name of its own, so that the node says which epilogue ran."""
 
 
 class _EulerSiddonImageFn(torch.autograd.Function):
     """``drr(rot, xyz, parameterization="euler_angles")`` for pose parameters that take a gradient, when the
     similarity is computed OUTSIDE the render (reference registration.py:32-42 with any criterion of
-    metrics.py, or a user's own loss): forward ddrr_pose_raygen_forward (pose -> matrix -> rays, and the
-    clears of the render behind it) + the brick kernel with its record + the image from the record -- three
-    launches for five; backward ddrr_siddon_backward_pose_euler -- one for three (a fill, the record's ray
+    metrics.py, or a user's own loss): forward ``_euler_siddon_render`` with the record and the image from it --
+    three launches for five; backward ddrr_siddon_backward_pose_euler -- one for three (a fill, the record's ray
     gradients reduced to dL/dMw, matrix -> pose parameters).  Same arithmetic per element as
     ``_PoseEulerFn`` + ``_SiddonPoseFn``; (rot, xyz) -> image (B, N)."""
 
     @staticmethod
     def forward(ctx, rot, xyz, volume, reorient34, P, Ainv, axes, cfg):
-        B, N = rot.shape[0], P.shape[0]
-        aux = ops.brick_record_buffer(B, N, rot.device)
-        launch_ws = ops.launch_workspace(volume.shape, volume.device)
-        Mw, source, target, img = ops.pose_raygen_forward(rot, xyz, axes, reorient34, Ainv, P,
-                                                          clear=aux, clear_launch_ws=launch_ws)
-        out, _ = ops.siddon_forward_bricks(
-            volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"],
-            want_aux=True, storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), aux=aux,
-            launch_ws=launch_ws, cleared=True)
+        Mw, source, _, _, aux, out = _euler_siddon_render(rot, xyz, volume, reorient34, P, Ainv, axes, cfg,
+                                                          want_image=True)
         ctx.axes, ctx.cfg = axes, cfg
         ctx.save_for_backward(rot, xyz, reorient34, P, Ainv, Mw, source, aux)
         return out
