@@ -36,6 +36,7 @@ POLYRIGID_ABI_VERSION = 1
 JACOBIAN_ABI_VERSION = 1
 PROX_ABI_VERSION = 1
 WNCC_ABI_VERSION = 1
+WLM_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -497,3 +498,35 @@ def get_wncc_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _wncc_lib = wncc_library(WNCC_LIB_PATH)
     return _wncc_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_wlm_hip.so
+# Levenberg-Marquardt registration with a per-pixel weight: the weighted normal-equations sums and the step
+# (C ABI: include/diffdrr_wlm_hip.h)
+WLM_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_wlm_hip.so")
+WLM_HEADER = Header.read("diffdrr_wlm_hip.h", "ddrr_wlm", WLM_ABI_VERSION)
+_WLM_SIGNATURES, _WLM_RESTYPES, WLM_EXPORTS = WLM_HEADER.tables()
+WLM_SUMS, WLM_GROUP_RAYS, WLM_STATE_DOUBLES, WLM_MAX_POSES = WLM_HEADER.constants(
+    "SUMS", "GROUP_RAYS", "STATE_DOUBLES", "MAX_POSES")
+
+
+def wlm_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_wlm_hip.h."""
+    return DdrrLibrary(path, WLM_HEADER)
+
+
+_wlm_lib: DdrrLibrary | None = None
+
+
+def get_wlm_lib() -> DdrrLibrary:
+    """The weighted Levenberg-Marquardt library, loaded on first use.  Raises if it has not been built."""
+    global _wlm_lib
+    if _wlm_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(WLM_LIB_PATH):
+            raise RuntimeError(
+                f"{WLM_LIB_PATH} is missing: the weighted Levenberg-Marquardt kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _wlm_lib = wlm_library(WLM_LIB_PATH)
+    return _wlm_lib

@@ -79,9 +79,9 @@ DDRR_HD double slice_sum(const float *u, int count, int k, int slice) {
     return v;
 }
 
-// ncc, A (upper triangle) and g of the residual z(x) - z(f) from the 44 sums: step 1 of ddrr_lm_step
-DDRR_HD void normal_equations(const double *S, int N, double ncc_eps, double &ncc, double A[21], double g[6]) {
-    const double n = (double)N;
+// ncc, A (upper triangle) and g of the residual z(x) - z(f) from the 44 sums: step 1 of ddrr_lm_step, with n
+// the number of rays (wlm_core.h: the sum of their weights, every sum weighted)
+DDRR_HD void normal_equations(const double *S, double n, double ncc_eps, double &ncc, double A[21], double g[6]) {
     const double mx = S[kSumM] / n, mf = S[kSumM + 1] / n;
     const double vx = S[kSumM + 2] / n - mx * mx, vf = S[kSumM + 3] / n - mf * mf;
     const double sx = sqrt(vx + ncc_eps), sf = sqrt(vf + ncc_eps);
@@ -100,6 +100,10 @@ DDRR_HD void normal_equations(const double *S, int N, double ncc_eps, double &nc
         for (int q = p; q < 6; ++q)
             A[tri(p, q)] = (S[tri(p, q)] - S[kSumA + p] * S[kSumA + q] / n - (2.0 - rho) * u[p] * u[q] / n) /
                            (sx * sx);
+}
+
+DDRR_HD void normal_equations(const double *S, int N, double ncc_eps, double &ncc, double A[21], double g[6]) {
+    normal_equations(S, (double)N, ncc_eps, ncc, A, g);
 }
 
 // (A + lambda diag(A) + tiny I) delta = -g by Cholesky; false (delta = 0) on a pivot that is not > 0
@@ -143,11 +147,10 @@ DDRR_HD bool solve_damped(const double A[21], const double g[6], double lambda, 
     return true;
 }
 
-// steps 1-4 of ddrr_lm_step for one pose, from its summed S
-DDRR_HD void step_pose(const double *S, int N, double ncc_eps, double up, double down, double lambda_min,
-                       double lambda_max, double *st, float *rot, float *xyz, float *ncc_out) {
-    double ncc, A[21], g[6];
-    normal_equations(S, N, ncc_eps, ncc, A, g);
+// steps 2-4 of ddrr_lm_step for one pose, from the rendered pose's ncc, A and g
+DDRR_HD void judge_and_solve(double ncc, const double A[21], const double g[6], double up, double down,
+                             double lambda_min, double lambda_max, double *st, float *rot, float *xyz,
+                             float *ncc_out) {
     double lambda = st[kStLambda];
     if (st[kStValid] == 0.0 || ncc > st[kStNcc]) {
 #pragma unroll
@@ -176,6 +179,14 @@ DDRR_HD void step_pose(const double *S, int N, double ncc_eps, double up, double
         xyz[p] = (float)(st[kStTheta + 3 + p] + delta[3 + p]);
     }
     *ncc_out = (float)st[kStNcc];
+}
+
+// steps 1-4 of ddrr_lm_step for one pose, from its summed S
+DDRR_HD void step_pose(const double *S, int N, double ncc_eps, double up, double down, double lambda_min,
+                       double lambda_max, double *st, float *rot, float *xyz, float *ncc_out) {
+    double ncc, A[21], g[6];
+    normal_equations(S, N, ncc_eps, ncc, A, g);
+    judge_and_solve(ncc, A, g, up, down, lambda_min, lambda_max, st, rot, xyz, ncc_out);
 }
 
 }  // namespace ddrr_lm

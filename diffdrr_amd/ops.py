@@ -1802,6 +1802,86 @@ def lm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, dam
     return out
 
 
+# ------------------------------------------------- weighted Levenberg-Marquardt (libdiffdrr_wlm_hip.so)
+def _launch_wlm(name, device, *args):
+    """:func:`_launch` through the weighted Levenberg-Marquardt library."""
+    _launch_on(_lib.get_wlm_lib(), name, device, args)
+
+
+def _query_wlm(name, *args):
+    return _lib.get_wlm_lib().query(name, *args)
+
+
+def wlm_workspace(B, N, device):
+    """The (uninitialised) per-workgroup partial sums of :func:`wlm_normal_sums` for B poses of N rays:
+    (B, ceil(N / 1024), 45) float64."""
+    n = int(_query_wlm("ddrr_wlm_workspace_bytes", int(B), int(N))) // 8
+    return torch.empty(n, dtype=torch.float64, device=device).view(B, -1, _lib.WLM_SUMS) if n else \
+        torch.empty(B, 0, _lib.WLM_SUMS, dtype=torch.float64, device=device)
+
+
+def wlm_normal_sums(aux, fixed, weight, *, source, Mw, Ainv, P, rot, xyz, axes, reorient34, eps=1e-8,
+                    with_img_path=True, ws=None, want_jacobian=False):
+    """The 45 weighted normal-equations sums of every rendered pose from the brick kernel's blocked record ``aux``
+    (include/diffdrr_wlm_hip.h ddrr_wlm_normal_sums; ``fixed`` and ``weight`` ((B | 1), N) float32, weights >= 0
+    and finite -- not looked for here; the rest as :func:`pose_raygen_forward` made them)
+    -> (ws (B, G, 45) float64 per-workgroup partials, jac (B, N, 6) float32 | None)."""
+    _require_gpu(rot)
+    B, N = rot.shape[0], P.shape[0]
+    dev = rot.device
+    if fixed.dim() != 2 or fixed.shape[0] not in (1, B) or fixed.shape[1] != N or fixed.dtype != torch.float32:
+        raise ValueError(f"wlm_normal_sums: a float32 fixed image of shape (1 | {B}, {N}) expected, got "
+                         f"{tuple(fixed.shape)} {fixed.dtype}")
+    if not torch.is_tensor(weight) or weight.dim() != 2 or weight.shape[0] not in (1, B) or weight.shape[1] != N \
+            or weight.dtype != torch.float32:
+        raise ValueError(f"wlm_normal_sums: a float32 weight of shape (1 | {B}, {N}) expected, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__} "
+                         f"{getattr(weight, 'dtype', '')}")
+    for what, t in (("fixed image", fixed), ("weight", weight)):
+        if t.device != dev:
+            raise ValueError(f"wlm_normal_sums: the {what} must live on the poses' device ({dev}), got {t.device}")
+    if B > _lib.WLM_MAX_POSES:
+        raise ValueError(f"wlm_normal_sums: at most {_lib.WLM_MAX_POSES} poses, got {B}")
+    fixed, weight, source = fixed.contiguous(), weight.contiguous(), source.contiguous()
+    held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
+    if ws is None:
+        ws = wlm_workspace(B, N, dev)
+    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != wlm_workspace(B, N, "meta").numel():
+        raise ValueError("wlm_normal_sums: ws must be what wlm_workspace(B, N, device) returns")
+    jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
+    if B and N:
+        _launch_wlm("ddrr_wlm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(),
+                    0 if (fixed.shape[0] == 1 and B != 1) else N, weight.data_ptr(),
+                    0 if (weight.shape[0] == 1 and B != 1) else N, source.data_ptr(), *chain, B, N, float(eps),
+                    int(bool(with_img_path)), ws.data_ptr(), _ptr(jac))
+    return ws, jac
+
+
+def wlm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, damping_min=1e-7, damping_max=1e6,
+             out=None):
+    """:func:`lm_step` on the weighted sums of :func:`wlm_normal_sums` (include/diffdrr_wlm_hip.h ddrr_wlm_step):
+    the same state (:func:`lm_state`), whose column 37 takes the sum of the weights of the render just judged
+    -> the best weighted NCC per pose (B,) float32."""
+    _require_gpu(rot)
+    B = rot.shape[0]
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, 3):
+            raise ValueError("wlm_step: contiguous float32 (B, 3) pose parameters")
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (B, _lib.WLM_STATE_DOUBLES):
+        raise ValueError(f"wlm_step: state must be a contiguous float64 (B, {_lib.WLM_STATE_DOUBLES}) tensor")
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != wlm_workspace(B, N, "meta").numel():
+        raise ValueError("wlm_step: ws must be what wlm_workspace(B, N, device) returns")
+    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
+        raise ValueError("wlm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=rot.device)
+    if B:
+        _launch_wlm("ddrr_wlm_step", rot.device, ws.data_ptr(), state.data_ptr(), rot.data_ptr(), xyz.data_ptr(), B,
+                    int(N), float(ncc_eps), float(up), float(down), float(damping_min), float(damping_max),
+                    out.data_ptr())
+    return out
+
+
 # ------------------------------------------------- weighted (masked) NCC (libdiffdrr_wncc_hip.so)
 def _launch_wncc(name, device, *args):
     """:func:`_launch` through the weighted NCC library."""

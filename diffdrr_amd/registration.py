@@ -275,6 +275,43 @@ def normal_equations_reference(J: torch.Tensor, x: torch.Tensor, f: torch.Tensor
     return (zx * zf).mean(-1), Jr.transpose(-1, -2) @ Jr, (Jr * r.unsqueeze(-1)).sum(-2)
 
 
+def weighted_normal_equations_reference(J: torch.Tensor, x: torch.Tensor, f: torch.Tensor, w: torch.Tensor,
+                                        eps: float = 1e-5):
+    """:func:`normal_equations_reference` under per-pixel weights ``w`` ((..., N), >= 0), in float64 torch: with
+    ``Sw = sum w``, the weighted mean and the weighted biased variance in ``z_w(v) = (v - mean_w v) /
+    sqrt(var_w v + eps)``, and the residual ``r = sqrt(w) (z_w(x) - z_w(f))`` -> ``(ncc, A, g, Sw)`` = (sum w z_w(x)
+    z_w(f) / Sw, J_r^T J_r with the exact J_r = dr / dtheta, J_r^T r, sum w).  ``1/2 |r|^2 = Sw (1 - ncc)`` up to
+    ``eps``.  Pixels of weight 0 are selected out (``torch.where``), not multiplied: ``x`` and ``f`` may hold NaN
+    or Inf there.  With ``w = 1`` it returns what the unweighted reference returns; a pose with ``Sw = 0`` gets
+    ncc 0, A 0, g 0.  ``ddrr_wlm_step`` forms the same from 45 sums (include/diffdrr_wlm_hip.h); this function is
+    the yardstick of its tests."""
+    J, x, f, w = J.double(), x.double(), f.double(), w.double()
+    on = w != 0
+    zero = torch.zeros_like(x)
+    x, f = torch.where(on, x, zero), torch.where(on, f, zero)
+    J = torch.where(on.unsqueeze(-1), J, torch.zeros_like(J))
+    Sw = w.sum(-1, keepdim=True)
+    some = Sw > 0
+    n = torch.where(some, Sw, torch.ones_like(Sw))
+    mx, mf = (w * x).sum(-1, keepdim=True) / n, (w * f).sum(-1, keepdim=True) / n
+    vx, vf = (w * (x - mx) ** 2).sum(-1, keepdim=True) / n, (w * (f - mf) ** 2).sum(-1, keepdim=True) / n
+    sx, sf = (vx + eps).sqrt(), (vf + eps).sqrt()
+    zx, zf = torch.where(on, (x - mx) / sx, zero), torch.where(on, (f - mf) / sf, zero)
+    # dz_n / dtheta = (J_n - mean_w J) / s_x - z_n (sum w z J) / (Sw s_x); a row of r carries sqrt(w_n)
+    wJ = w.unsqueeze(-1) * J
+    Jc = J - wJ.sum(-2, keepdim=True) / n.unsqueeze(-1)
+    zJ = (zx.unsqueeze(-1) * wJ).sum(-2, keepdim=True)
+    Jz = Jc / sx.unsqueeze(-1) - zx.unsqueeze(-1) * zJ / (n * sx).unsqueeze(-1)
+    Jz = torch.where(on.unsqueeze(-1), Jz, torch.zeros_like(Jz))
+    r = zx - zf
+    A = (w.unsqueeze(-1) * Jz).transpose(-1, -2) @ Jz
+    g = (w.unsqueeze(-1) * Jz * r.unsqueeze(-1)).sum(-2)
+    ncc = (w * zx * zf).sum(-1) / n.squeeze(-1)
+    keep = some.squeeze(-1)
+    return (torch.where(keep, ncc, torch.zeros_like(ncc)), torch.where(keep[..., None, None], A, torch.zeros_like(A)),
+            torch.where(keep[..., None], g, torch.zeros_like(g)), Sw.squeeze(-1))
+
+
 class LevenbergMarquardt:
     """Levenberg-Marquardt on the least-squares form of the global NCC, ``1/2 |z(drr) - z(fixed)|^2``,
     for the Euler pose parameters of ``reg`` -- the second-order counterpart of the reference's
@@ -298,6 +335,16 @@ class LevenbergMarquardt:
     most ``DRR.FUSED_NCC_MAX_POSES`` poses; ``fixed`` ((1 | B), 1, H, W) float32.  Anything else raises
     ``ValueError`` naming the condition.
 
+    ``weight`` ((1 | B), 1, H, W) float32 on the parameters' device, finite and >= 0 (checked once, here; then
+    read in place at every step, as ``fixed`` is): the weighted (masked) problem of include/diffdrr_wlm_hip.h
+    -- the residual ``sqrt(w) (z_w(drr) - z_w(fixed))`` with the weighted mean and variance, the objective of
+    ``DRR.ncc(..., weight=)``.  Pixels of weight 0 (collimator, dead pixels, instruments) are selected out of every
+    sum: ``fixed`` may hold anything there.  ``step()`` is the same four launches with ``ddrr_wlm_normal_sums``
+    and ``ddrr_wlm_step`` in place of the two ``ddrr_lm_*`` entries, and returns the best weighted NCC;
+    ``weight_sum`` is the sum of the weights of the last render per pose.  A pose whose weights are all 0 never
+    moves and reports NCC 0.  Editing the weight between steps makes "best so far" compare different objectives:
+    build a new object instead.  Without ``weight`` nothing changes: the unweighted kernels run.
+
     ``graph=True`` (the step captured as one HIP graph, as ``GraphedIteration`` captures its iteration) is
     not built: it raises ``NotImplementedError``.  Nothing in a step stands in its way -- no launch depends
     on data, nothing is read back -- but the render's record is summed with float atomics, so a captured
@@ -305,7 +352,7 @@ class LevenbergMarquardt:
 
     def __init__(self, reg: Registration, fixed: torch.Tensor, damping: float = 1.0, up: float = 4.0,
                  down: float = 1.0 / 3.0, damping_min: float = 1e-7, damping_max: float = 1e6, eps: float = 1e-5,
-                 graph: bool = False):
+                 graph: bool = False, weight: torch.Tensor | None = None):
         from . import ops
         from .pose import _check_convention
         from .renderers import Siddon
@@ -360,11 +407,24 @@ class LevenbergMarquardt:
             refuse(f"fixed must be a float32 ((1 | {B}), 1, {H}, {W}) tensor")
         if fixed.device != rot.device:
             refuse(f"fixed must live on the parameters' device ({rot.device}), got {fixed.device}")
+        if weight is not None:
+            if not torch.is_tensor(weight) or weight.dtype != torch.float32:
+                refuse(f"weight must be a float32 tensor, got {getattr(weight, 'dtype', type(weight).__name__)}")
+            if weight.dim() != 4 or weight.shape[0] not in (1, B) or tuple(weight.shape[1:]) != (1, H, W):
+                refuse(f"weight must have the shape ((1 | {B}), 1, {H}, {W}), got {tuple(weight.shape)}")
+            if weight.device != rot.device:
+                refuse(f"weight must live on the parameters' device ({rot.device}), got {weight.device}")
+            if not bool(torch.isfinite(weight).all()):
+                refuse("weight must be finite (it holds NaN or Inf)")
+            if bool((weight < 0).any()):
+                refuse("weight must not be negative")
         self.B, self.N = B, H * W
         self.fixed = fixed.detach().reshape(fixed.shape[0], H * W).contiguous()
+        # (a view where the caller's tensor is contiguous: read in place, as the fixed image is)
+        self.weight = None if weight is None else weight.detach().reshape(weight.shape[0], H * W).contiguous()
         dev = rot.device
         self._state = ops.lm_state(B, damping, dev)
-        self._ws = ops.lm_workspace(B, self.N, dev)
+        self._ws = ops.lm_workspace(B, self.N, dev) if weight is None else ops.wlm_workspace(B, self.N, dev)
         self._aux = ops.brick_record_buffer(B, self.N, dev)
         self._ncc = torch.zeros(B, dtype=torch.float32, device=dev)
         self.steps_done = 0
@@ -384,6 +444,11 @@ class LevenbergMarquardt:
         from . import ops
 
         args, kw = self._render()
+        hyper = dict(ncc_eps=self.eps, up=self.up, down=self.down, damping_min=self.damping_min,
+                     damping_max=self.damping_max)
+        if self.weight is not None:
+            ops.wlm_normal_sums(args.pop("aux"), self.fixed, self.weight, **args, **kw, ws=self._ws)
+            return ops.wlm_step(self._ws, self._state, args["rot"], args["xyz"], self.N, **hyper, out=out)
         ops.lm_normal_sums(args.pop("aux"), self.fixed, **args, **kw, ws=self._ws)
         return ops.lm_step(self._ws, self._state, args["rot"], args["xyz"], self.N, ncc_eps=self.eps, up=self.up,
                            down=self.down, damping_min=self.damping_min, damping_max=self.damping_max, out=out)
@@ -427,6 +492,12 @@ class LevenbergMarquardt:
     @property
     def best_ncc(self) -> torch.Tensor:
         return self._state[:, 6].detach()
+
+    @property
+    def weight_sum(self) -> torch.Tensor:
+        """(B,) float64: the sum of the weights of the last render judged, per pose (0 before the first step,
+        and always without ``weight``)."""
+        return self._state[:, 37].detach()
 
     @property
     def accepted(self) -> torch.Tensor:
