@@ -39,5 +39,7 @@ from .reconstruction import (  # noqa: F401
     tv_divergence_adjoint,
     tv_gradient_operator,
 )
-from .registration import GraphedIteration, LevenbergMarquardt, PoseAdam, Registration  # noqa: F401
+from .registration import (  # noqa: F401
+    GraphedIteration, LevenbergMarquardt, MultiViewLevenbergMarquardt, PoseAdam, Registration,
+)
 from .renderers import Siddon, Trilinear  # noqa: F401

@@ -37,6 +37,7 @@ JACOBIAN_ABI_VERSION = 1
 PROX_ABI_VERSION = 1
 WNCC_ABI_VERSION = 1
 WLM_ABI_VERSION = 1
+MVLM_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -530,3 +531,35 @@ def get_wlm_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _wlm_lib = wlm_library(WLM_LIB_PATH)
     return _wlm_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_mvlm_hip.so
+# multi-view (biplane) Levenberg-Marquardt registration: the rays of S starts seen from V views, the sums of the
+# S * V poses and the step on the sums added over a start's views (C ABI: include/diffdrr_mvlm_hip.h)
+MVLM_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_mvlm_hip.so")
+MVLM_HEADER = Header.read("diffdrr_mvlm_hip.h", "ddrr_mvlm", MVLM_ABI_VERSION)
+_MVLM_SIGNATURES, _MVLM_RESTYPES, MVLM_EXPORTS = MVLM_HEADER.tables()
+MVLM_SUMS, MVLM_GROUP_RAYS, MVLM_STATE_DOUBLES, MVLM_MAX_POSES = MVLM_HEADER.constants(
+    "SUMS", "GROUP_RAYS", "STATE_DOUBLES", "MAX_POSES")
+
+
+def mvlm_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_mvlm_hip.h."""
+    return DdrrLibrary(path, MVLM_HEADER)
+
+
+_mvlm_lib: DdrrLibrary | None = None
+
+
+def get_mvlm_lib() -> DdrrLibrary:
+    """The multi-view Levenberg-Marquardt library, loaded on first use.  Raises if it has not been built."""
+    global _mvlm_lib
+    if _mvlm_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(MVLM_LIB_PATH):
+            raise RuntimeError(
+                f"{MVLM_LIB_PATH} is missing: the multi-view Levenberg-Marquardt kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _mvlm_lib = mvlm_library(MVLM_LIB_PATH)
+    return _mvlm_lib

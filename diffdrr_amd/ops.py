@@ -1882,6 +1882,127 @@ def wlm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, da
     return out
 
 
+# ------------------------------------------------- multi-view Levenberg-Marquardt (libdiffdrr_mvlm_hip.so)
+def _launch_mvlm(name, device, *args):
+    """:func:`_launch` through the multi-view Levenberg-Marquardt library."""
+    _launch_on(_lib.get_mvlm_lib(), name, device, args)
+
+
+def _query_mvlm(name, *args):
+    return _lib.get_mvlm_lib().query(name, *args)
+
+
+def _mvlm_views(name, rot, xyz, reorient_v):
+    """(S, V) of (S, 3) parameters and (V, 3, 4) float32 reorients; refuses what the entries would misread."""
+    S = rot.shape[0]
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or t.shape != (S, 3):
+            raise ValueError(f"{name}: float32 (S, 3) pose parameters expected, got {tuple(t.shape)} {t.dtype}")
+    if reorient_v.dim() != 3 or reorient_v.shape[0] < 1 or tuple(reorient_v.shape[1:]) != (3, 4) \
+            or reorient_v.dtype != torch.float32:
+        raise ValueError(f"{name}: reorient_v must be a float32 (V, 3, 4) tensor with V >= 1, got "
+                         f"{tuple(reorient_v.shape)} {reorient_v.dtype}")
+    V = reorient_v.shape[0]
+    if S * V > _lib.MVLM_MAX_POSES:
+        raise ValueError(f"{name}: at most {_lib.MVLM_MAX_POSES} poses (S * V), got {S} * {V}")
+    return S, V
+
+
+def mvlm_workspace(S, V, N, device):
+    """The (uninitialised) per-workgroup partial sums of :func:`mvlm_normal_sums` for S starts seen from V views
+    with N rays: (S * V, ceil(N / 1024), 44) float64."""
+    n = int(_query_mvlm("ddrr_mvlm_workspace_bytes", int(S), int(V), int(N))) // 8
+    return torch.empty(n, dtype=torch.float64, device=device).view(S * V, -1, _lib.MVLM_SUMS) if n else \
+        torch.empty(S * V, 0, _lib.MVLM_SUMS, dtype=torch.float64, device=device)
+
+
+def mvlm_raygen(rot, xyz, axes, reorient_v, Ainv, P, *, clear=None, clear_launch_ws=None):
+    """:func:`pose_raygen_forward` for S starts seen from V views in one launch (include/diffdrr_mvlm_hip.h
+    ddrr_mvlm_raygen): pose ``b = s * V + v`` is the Euler pose (rot[s], xyz[s]) with the reorient ``reorient_v[v]``
+    -> (Mw (S V, 3, 4), source_v (S V, 1, 3), target_v (S V, N, 3), img (S V, N)).  ``clear`` and ``clear_launch_ws``
+    as there."""
+    _require_gpu(rot)
+    S, V = _mvlm_views("mvlm_raygen", rot, xyz, reorient_v)
+    N, B = P.shape[0], S * V
+    rot, xyz, reorient_v, Ainv, P = (t.contiguous() for t in (rot, xyz, reorient_v, Ainv, P))
+    dev = rot.device
+    Mw = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
+    source = torch.empty(B, 1, 3, dtype=torch.float32, device=dev)
+    target = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+    img = torch.empty(B, N, dtype=torch.float32, device=dev)
+    if not _empty(B, N):
+        _launch_mvlm("ddrr_mvlm_raygen", dev, rot.data_ptr(), xyz.data_ptr(), *axes, reorient_v.data_ptr(),
+                     Ainv.data_ptr(), P.data_ptr(), S, V, N, Mw.data_ptr(), source.data_ptr(), target.data_ptr(),
+                     img.data_ptr(), _ptr(clear), 0 if clear is None else clear.numel(), _ptr(clear_launch_ws))
+    elif clear is not None or clear_launch_ws is not None:
+        raise ValueError("mvlm_raygen: nothing is launched for an empty batch, nothing is cleared")
+    return Mw, source, target, img
+
+
+def mvlm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient_v, *, eps=1e-8, with_img_path=True,
+                     ws=None, want_jacobian=False):
+    """The 44 normal-equations sums of the S * V rendered poses from the brick kernel's blocked record ``aux``
+    (include/diffdrr_mvlm_hip.h ddrr_mvlm_normal_sums; ``fixed`` (V, N) float32: one image per view; ``rot``,
+    ``xyz`` (S, 3); ``reorient_v`` (V, 3, 4); the rest as :func:`mvlm_raygen` made them)
+    -> (ws (S V, G, 44) float64 per-workgroup partials, jac (S V, N, 6) float32 | None)."""
+    _require_gpu(rot)
+    S, V = _mvlm_views("mvlm_normal_sums", rot, xyz, reorient_v)
+    N, B = P.shape[0], S * V
+    dev = rot.device
+    if not torch.is_tensor(fixed) or fixed.shape != (V, N) or fixed.dtype != torch.float32:
+        raise ValueError(f"mvlm_normal_sums: a float32 fixed image per view, ({V}, {N}), expected, got "
+                         f"{tuple(fixed.shape) if torch.is_tensor(fixed) else type(fixed).__name__} "
+                         f"{getattr(fixed, 'dtype', '')}")
+    if fixed.device != dev:
+        raise ValueError(f"mvlm_normal_sums: the fixed images must live on the poses' device ({dev}), got "
+                         f"{fixed.device}")
+    if Mw.shape[0] != B or source.shape[0] != B:
+        raise ValueError(f"mvlm_normal_sums: Mw and source of {B} poses (S * V) expected, got {Mw.shape[0]} and "
+                         f"{source.shape[0]}")
+    fixed, source = fixed.contiguous(), source.contiguous()
+    held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient_v)
+    if ws is None:
+        ws = mvlm_workspace(S, V, N, dev)
+    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != mvlm_workspace(S, V, N, "meta").numel():
+        raise ValueError("mvlm_normal_sums: ws must be what mvlm_workspace(S, V, N, device) returns")
+    jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
+    if B and N:
+        _launch_mvlm("ddrr_mvlm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), source.data_ptr(), *chain, S, V,
+                     N, float(eps), int(bool(with_img_path)), ws.data_ptr(), _ptr(jac))
+    return ws, jac
+
+
+def mvlm_step(ws, state, rot, xyz, V, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, damping_min=1e-7, damping_max=1e6,
+              out=None, ncc_views=None):
+    """:func:`lm_step` for S starts on the sums of their V views (include/diffdrr_mvlm_hip.h ddrr_mvlm_step): the
+    views' normal equations are added, the mean NCC is judged against ``state`` ((S, 40), :func:`lm_state`), the
+    next trial is written into ``rot``, ``xyz`` (S, 3) IN PLACE -> the best mean NCC per start (S,) float32.
+    ``ncc_views`` ((S, V) float32, optional) receives the NCC of every view of the render just judged."""
+    _require_gpu(rot)
+    S, V = rot.shape[0], int(V)
+    if V < 1 or S * V > _lib.MVLM_MAX_POSES:
+        raise ValueError(f"mvlm_step: V >= 1 and at most {_lib.MVLM_MAX_POSES} poses (S * V) expected, got {S} * {V}")
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (S, 3):
+            raise ValueError("mvlm_step: contiguous float32 (S, 3) pose parameters")
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (S, _lib.MVLM_STATE_DOUBLES):
+        raise ValueError(f"mvlm_step: state must be a contiguous float64 (S, {_lib.MVLM_STATE_DOUBLES}) tensor")
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != mvlm_workspace(S, V, N, "meta").numel():
+        raise ValueError("mvlm_step: ws must be what mvlm_workspace(S, V, N, device) returns")
+    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
+        raise ValueError("mvlm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
+    if ncc_views is not None and (ncc_views.dtype != torch.float32 or not ncc_views.is_contiguous()
+                                  or ncc_views.shape != (S, V) or ncc_views.device != rot.device):
+        raise ValueError(f"mvlm_step: ncc_views must be a contiguous float32 ({S}, {V}) tensor on the poses' device")
+    if out is None:
+        out = torch.empty(S, dtype=torch.float32, device=rot.device)
+    if S:
+        _launch_mvlm("ddrr_mvlm_step", rot.device, ws.data_ptr(), state.data_ptr(), rot.data_ptr(), xyz.data_ptr(), S,
+                     V, int(N), float(ncc_eps), float(up), float(down), float(damping_min), float(damping_max),
+                     out.data_ptr(), _ptr(ncc_views))
+    return out
+
+
 # ------------------------------------------------- weighted (masked) NCC (libdiffdrr_wncc_hip.so)
 def _launch_wncc(name, device, *args):
     """:func:`_launch` through the weighted NCC library."""

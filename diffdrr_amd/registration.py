@@ -503,3 +503,230 @@ class LevenbergMarquardt:
     def accepted(self) -> torch.Tensor:
         """(B,) bool: whether the last step's render became the best pose."""
         return self._state[:, 36] != 0
+
+
+# ------------------------------------------------------------------------------------------------ several views
+def relative_views(poses) -> torch.Tensor:
+    """The calibrated extrinsics ``E_v`` of V C-arm shots of ONE patient position (a ``RigidTransform`` of V poses,
+    or a (V, 4, 4) tensor) -> ``K_v = E_0^-1 E_v``, (V, 4, 4) float64: what ``MultiViewLevenbergMarquardt`` takes as
+    ``views``.  The parameters it optimises then describe view 0 (``K_0`` is the identity, exactly)."""
+    E = (poses.matrix if hasattr(poses, "matrix") else poses).detach().double()
+    if E.dim() != 3 or E.shape[0] < 1 or tuple(E.shape[1:]) != (4, 4):
+        raise ValueError(f"relative_views: (V, 4, 4) poses with V >= 1 expected, got {tuple(E.shape)}")
+    K = torch.linalg.solve(E[0], E)
+    K[0] = torch.eye(4, dtype=torch.float64, device=E.device)
+    return K
+
+
+def view_poses(rot: torch.Tensor, xyz: torch.Tensor, views: torch.Tensor, convention: str = "ZXY"):
+    """The S * V poses a multi-view registration renders, as a ``RigidTransform``: pose ``s * V + v`` is
+    ``M(rot[s], xyz[s]) @ views[v]`` with ``M`` the Euler pose of ``convert(..., parameterization="euler_angles")``
+    (radians), in the parameters' dtype and differentiable in torch.  ``drr(view_poses(...))`` is what a first-order
+    multi-view loop renders through the matrix route, and the yardstick of the multi-view kernels' tests."""
+    from .pose import RigidTransform
+
+    M = convert(rot, xyz, parameterization="euler_angles", convention=convention).matrix  # (S, 4, 4)
+    K = views.to(dtype=M.dtype, device=M.device)
+    return RigidTransform(torch.einsum("sij,vjk->svik", M, K).reshape(-1, 4, 4))
+
+
+def multiview_normal_equations_reference(J: torch.Tensor, x: torch.Tensor, f: torch.Tensor, eps: float = 1e-5):
+    """The definition of what a multi-view Levenberg-Marquardt step solves, in float64 torch: the residual of a
+    start is the stack over its views of ``z(x_v) - z(f_v)``, every view normalised on its own
+    (:func:`normal_equations_reference` per view), with ``J`` (S, V, N, 6) the derivative of ``x`` (S, V, N) with
+    respect to the start's six parameters and ``f`` (V, N) one fixed image per view
+    -> ``(ncc, A, g, ncc_views)`` = (mean_v ncc_v (S,), sum_v A_v (S, 6, 6), sum_v g_v (S, 6), ncc_v (S, V)).
+    ``ddrr_mvlm_step`` forms the same (include/diffdrr_mvlm_hip.h); this function is the yardstick of its tests."""
+    ncc, A, g = normal_equations_reference(J, x, f.double().expand(x.shape), eps)
+    return ncc.mean(-1), A.sum(-3), g.sum(-2), ncc
+
+
+class MultiViewLevenbergMarquardt:
+    """Levenberg-Marquardt for ONE set of six Euler pose parameters per start seen from several calibrated views
+    (a biplane pair, a few C-arm shots of one patient position): the objective of a start is
+    ``sum_v 1/2 |z(drr_v) - z(fixed_v)|^2``, every view normalised on its own, and the normal equations of the
+    views are added before the step is judged and solved.  One view cannot determine the translation along its
+    own viewing direction; a second one can.
+
+        K = relative_views(extrinsics)                    # (V, 4, 4): E_0^-1 E_v, view 0 is the parameters' view
+        lm = MultiViewLevenbergMarquardt(reg, fixed, K)   # fixed (V, 1, H, W), reg: S starts
+        for _ in range(30):
+            ncc = lm.step()                               # (S,) best mean NCC over the views so far
+        lm.commit()
+
+    View ``v`` renders the pose ``M(theta_s) @ views[v]`` (:func:`view_poses`): the existing Euler pose with
+    ``(views[v] @ reorient)[:3]``, formed in float64 and rounded once, in place of the detector's reorient.
+    ``step()`` is four launches and no host synchronisation -- ``ddrr_mvlm_raygen`` with the clears, the brick
+    kernel with its record and no image (S * V poses), ``ddrr_mvlm_normal_sums`` and ``ddrr_mvlm_step``
+    (include/diffdrr_mvlm_hip.h) -- and returns the best mean NCC per start; ``view_ncc`` (S, V) holds the NCC of
+    every view of the render last judged.  ``commit``, ``damping``, ``best_parameters``, ``best_ncc`` and
+    ``accepted`` are ``LevenbergMarquardt``'s, per start; ``jacobian()`` is (S, V, N, 6).
+
+    Domain: that of ``LevenbergMarquardt``, with ``S * V <= DRR.FUSED_NCC_MAX_POSES``; ``views`` finite float
+    (V, 4, 4) with the bottom row (0, 0, 0, 1) and an orthonormal rotation block; ``fixed`` float32 (V, 1, H, W) on
+    the parameters' device, shared by the starts.  Anything else raises ``ValueError`` naming the condition.
+
+    Not built: pixel weights (``LevenbergMarquardt(weight=)`` has them for one view), a detector per view (all
+    views share the module's ``Detector``), the step as a captured HIP graph, and a fused multi-view ``DRR.ncc``
+    for a first-order loop (which renders ``view_poses(...)`` through the matrix route)."""
+
+    def __init__(self, reg: Registration, fixed: torch.Tensor, views: torch.Tensor, damping: float = 1.0,
+                 up: float = 4.0, down: float = 1.0 / 3.0, damping_min: float = 1e-7, damping_max: float = 1e6,
+                 eps: float = 1e-5):
+        from . import ops
+        from .pose import _check_convention
+        from .renderers import Siddon
+
+        self.reg = reg
+        self.up, self.down, self.damping_min, self.damping_max, self.eps = (
+            float(up), float(down), float(damping_min), float(damping_max), float(eps))
+        if not (self.up > 1.0 and 0.0 < self.down < 1.0 and 0.0 < self.damping_min <= self.damping_max < float("inf")
+                and self.damping_min <= float(damping) <= self.damping_max and self.eps >= 0.0):
+            raise ValueError("MultiViewLevenbergMarquardt: up > 1, 0 < down < 1, 0 < damping_min <= damping <= "
+                             "damping_max < inf and eps >= 0 expected")
+        drr = reg.drr
+        r, det = getattr(drr, "renderer", None), getattr(drr, "detector", None)
+        rot, xyz = reg._rotation, reg._translation
+
+        def refuse(what):
+            raise ValueError(f"MultiViewLevenbergMarquardt: {what}")
+
+        if reg.parameterization != "euler_angles":
+            refuse(f"parameterization must be 'euler_angles', not {reg.parameterization!r}")
+        _check_convention(reg.convention)
+        if not isinstance(r, Siddon):
+            refuse("the renderer must be Siddon")
+        if r.grid_path != "bricks":
+            refuse("the Siddon renderer must take the brick kernel (grid_path == 'bricks')")
+        if r.packed_record:
+            refuse("the packed backward record (packed_record=True) is not read; use the float record")
+        if drr.density.requires_grad:
+            refuse("the volume must not require a gradient")
+        if drr.patch_size is not None:
+            refuse("patch_size must be None")
+        if det.n_subsample is not None:
+            refuse("p_subsample must be None (a dense detector)")
+        if not drr.fuse_ray_generation:
+            refuse("fuse_ray_generation must be on")
+        for name, t in (("rotation", rot), ("translation", xyz)):
+            if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32 or not t.is_contiguous():
+                refuse(f"{name} must be a contiguous float32 (S, 3) parameter, got {tuple(t.shape)} {t.dtype}")
+            if t.device != drr.density.device or not ops.on_device(t):
+                refuse(f"{name} must live on the volume's device ({drr.density.device}), got {t.device}")
+        if rot.shape != xyz.shape:
+            refuse(f"rotation {tuple(rot.shape)} and translation {tuple(xyz.shape)} must have one shape")
+        S = rot.shape[0]
+        if not (torch.is_tensor(views) and views.is_floating_point() and views.dim() == 3 and views.shape[0] >= 1
+                and tuple(views.shape[1:]) == (4, 4)):
+            refuse(f"views must be a float (V, 4, 4) tensor with V >= 1, got "
+                   f"{tuple(views.shape) if torch.is_tensor(views) else type(views).__name__} "
+                   f"{getattr(views, 'dtype', '')}")
+        K = views.detach().to(device=rot.device, dtype=torch.float64)
+        if not bool(torch.isfinite(K).all()):
+            refuse("views must be finite (they hold NaN or Inf)")
+        if not bool((K[:, 3] == torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=K.device)).all()):
+            refuse("views must be rigid: the bottom row of every matrix must be (0, 0, 0, 1)")
+        R = K[:, :3, :3]
+        tol = 1e-5 if views.dtype == torch.float32 else 1e-9
+        if float((R @ R.mT - torch.eye(3, dtype=torch.float64, device=K.device)).abs().max()) > tol \
+                or bool((torch.linalg.det(R) < 0).any()):
+            refuse(f"views must be rigid: the rotation block of every matrix must be orthonormal (to {tol:g}) with "
+                   "determinant +1")
+        V = K.shape[0]
+        if not 0 < S * V <= drr.FUSED_NCC_MAX_POSES:
+            refuse(f"1 ... {drr.FUSED_NCC_MAX_POSES} rendered poses (starts x views) expected, got {S} x {V}")
+        H, W = det.height, det.width
+        if not (torch.is_tensor(fixed) and fixed.dim() == 4 and tuple(fixed.shape) == (V, 1, H, W)
+                and fixed.dtype == torch.float32):
+            refuse(f"fixed must be a float32 ({V}, 1, {H}, {W}) tensor, one image per view")
+        if fixed.device != rot.device:
+            refuse(f"fixed must live on the parameters' device ({rot.device}), got {fixed.device}")
+        self.S, self.V, self.N = S, V, H * W
+        self.views = K
+        # Ro_v = (K_v @ reorient)[:3], in float64, rounded once
+        self._reorient_v = (K @ det._reorient.detach().to(K))[:, :3, :].to(torch.float32).contiguous()
+        self.fixed = fixed.detach().reshape(V, H * W).contiguous()
+        dev = rot.device
+        self._state = ops.lm_state(S, damping, dev)
+        self._ws = ops.mvlm_workspace(S, V, self.N, dev)
+        self._aux = ops.brick_record_buffer(S * V, self.N, dev)
+        self._view_ncc = torch.zeros(S, V, dtype=torch.float32, device=dev)
+        self.steps_done = 0
+
+    # -- one render of the current parameters from every view with its record: the first two launches of a step
+    def _render(self):
+        from . import ops
+        from .renderers import _brick_axis, _brick_storage
+
+        drr = self.reg.drr
+        rot, xyz = self.reg._rotation.detach(), self.reg._translation.detach()
+        rot, _, P, Ainv, axes, cfg = drr._euler_args(rot, self.reg.convention, False)
+        B, volume = self.S * self.V, drr.density
+        launch_ws = ops.launch_workspace(volume.shape, volume.device)
+        Mw, source, target, img = ops.mvlm_raygen(rot, xyz, axes, self._reorient_v, Ainv, P, clear=self._aux,
+                                                  clear_launch_ws=launch_ws)
+        ops.siddon_forward_bricks(
+            volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"], want_aux=True,
+            storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=False, aux=self._aux,
+            launch_ws=launch_ws, cleared=True)
+        return dict(aux=self._aux, source=source, Mw=Mw, Ainv=Ainv, P=P, rot=rot, xyz=xyz, axes=axes,
+                    reorient_v=self._reorient_v), dict(eps=cfg["eps"], with_img_path=not cfg["stop_gradients"])
+
+    @torch.no_grad()
+    def step(self) -> torch.Tensor:
+        """Render the current parameters from every view, accept or reject them, write the next trial into them
+        -> the best mean NCC per start so far, (S,), detached."""
+        from . import ops
+
+        args, kw = self._render()
+        ops.mvlm_normal_sums(args.pop("aux"), self.fixed, **args, **kw, ws=self._ws)
+        out = ops.mvlm_step(self._ws, self._state, args["rot"], args["xyz"], self.V, self.N, ncc_eps=self.eps,
+                            up=self.up, down=self.down, damping_min=self.damping_min, damping_max=self.damping_max,
+                            ncc_views=self._view_ncc)
+        self.steps_done += 1
+        return out
+
+    @torch.no_grad()
+    def commit(self):
+        """Copy the best parameters of every start into ``reg``'s (a start that has not rendered yet keeps its
+        parameters)."""
+        valid = self._state[:, 35:36] != 0
+        best = self._state[:, :6].to(torch.float32)
+        self.reg._rotation.copy_(torch.where(valid, best[:, :3], self.reg._rotation))
+        self.reg._translation.copy_(torch.where(valid, best[:, 3:], self.reg._translation))
+
+    @torch.no_grad()
+    def jacobian(self) -> torch.Tensor:
+        """d image_v / d (rot, xyz) at the current parameters, (S, V, N, 6) float32: one render and
+        ``ddrr_mvlm_normal_sums`` with its per-ray output.  The optimiser's state is not touched."""
+        from . import ops
+
+        args, kw = self._render()
+        jac = ops.mvlm_normal_sums(args.pop("aux"), self.fixed, **args, **kw, want_jacobian=True)[1]
+        return jac.view(self.S, self.V, self.N, 6)
+
+    @property
+    def damping(self) -> torch.Tensor:
+        return self._state[:, 34].detach()
+
+    @property
+    def best_parameters(self):
+        """(rotation, translation) of the best parameters of every start so far, (S, 3) float32 each (copies)."""
+        best = self._state[:, :6].to(torch.float32)
+        return best[:, :3], best[:, 3:]
+
+    @property
+    def best_ncc(self) -> torch.Tensor:
+        """(S,) float64: the best mean NCC over the views of every start so far."""
+        return self._state[:, 6].detach()
+
+    @property
+    def accepted(self) -> torch.Tensor:
+        """(S,) bool: whether the last step's render became the best of its start."""
+        return self._state[:, 36] != 0
+
+    @property
+    def view_ncc(self) -> torch.Tensor:
+        """(S, V) float32: the NCC of every view of the render last judged, accepted or not (0 before the first
+        step)."""
+        return self._view_ncc.detach()
