@@ -41,5 +41,6 @@ from .reconstruction import (  # noqa: F401
 )
 from .registration import (  # noqa: F401
     GraphedIteration, LevenbergMarquardt, MultiViewLevenbergMarquardt, PoseAdam, Registration,
+    WeightedMultiViewLevenbergMarquardt,
 )
 from .renderers import Siddon, Trilinear  # noqa: F401

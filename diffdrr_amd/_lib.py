@@ -38,6 +38,7 @@ PROX_ABI_VERSION = 1
 WNCC_ABI_VERSION = 1
 WLM_ABI_VERSION = 1
 MVLM_ABI_VERSION = 1
+WMVLM_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -563,3 +564,36 @@ def get_mvlm_lib() -> DdrrLibrary:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _mvlm_lib = mvlm_library(MVLM_LIB_PATH)
     return _mvlm_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_wmvlm_hip.so
+# multi-view Levenberg-Marquardt registration with a pixel weight and a detector per view: the rays, the weighted
+# sums of the S * V poses and the step on the sums added over a start's non-empty views
+# (C ABI: include/diffdrr_wmvlm_hip.h)
+WMVLM_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_wmvlm_hip.so")
+WMVLM_HEADER = Header.read("diffdrr_wmvlm_hip.h", "ddrr_wmvlm", WMVLM_ABI_VERSION)
+_WMVLM_SIGNATURES, _WMVLM_RESTYPES, WMVLM_EXPORTS = WMVLM_HEADER.tables()
+WMVLM_SUMS, WMVLM_GROUP_RAYS, WMVLM_STATE_DOUBLES, WMVLM_MAX_POSES = WMVLM_HEADER.constants(
+    "SUMS", "GROUP_RAYS", "STATE_DOUBLES", "MAX_POSES")
+
+
+def wmvlm_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_wmvlm_hip.h."""
+    return DdrrLibrary(path, WMVLM_HEADER)
+
+
+_wmvlm_lib: DdrrLibrary | None = None
+
+
+def get_wmvlm_lib() -> DdrrLibrary:
+    """The weighted multi-view Levenberg-Marquardt library, loaded on first use.  Raises if it has not been built."""
+    global _wmvlm_lib
+    if _wmvlm_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(WMVLM_LIB_PATH):
+            raise RuntimeError(
+                f"{WMVLM_LIB_PATH} is missing: the weighted multi-view Levenberg-Marquardt kernels have not been "
+                "built. Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _wmvlm_lib = wmvlm_library(WMVLM_LIB_PATH)
+    return _wmvlm_lib

@@ -2003,6 +2003,162 @@ def mvlm_step(ws, state, rot, xyz, V, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0
     return out
 
 
+# ------------------------------- weighted multi-view Levenberg-Marquardt (libdiffdrr_wmvlm_hip.so)
+def _launch_wmvlm(name, device, *args):
+    """:func:`_launch` through the weighted multi-view Levenberg-Marquardt library."""
+    _launch_on(_lib.get_wmvlm_lib(), name, device, args)
+
+
+def _query_wmvlm(name, *args):
+    return _lib.get_wmvlm_lib().query(name, *args)
+
+
+def _wmvlm_views(name, rot, xyz, reorient_v, P):
+    """(S, V, N, P_stride) of (S, 3) parameters, (V, 3, 4) float32 reorients and the detector points, (N, 3) shared
+    by the views (stride 0) or (V, N, 3) (stride 3 N); refuses what the entries would misread."""
+    S = rot.shape[0]
+    dev = rot.device
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or t.shape != (S, 3):
+            raise ValueError(f"{name}: float32 (S, 3) pose parameters expected, got {tuple(t.shape)} {t.dtype}")
+    if reorient_v.dim() != 3 or reorient_v.shape[0] < 1 or tuple(reorient_v.shape[1:]) != (3, 4) \
+            or reorient_v.dtype != torch.float32:
+        raise ValueError(f"{name}: reorient_v must be a float32 (V, 3, 4) tensor with V >= 1, got "
+                         f"{tuple(reorient_v.shape)} {reorient_v.dtype}")
+    V = reorient_v.shape[0]
+    if S * V > _lib.WMVLM_MAX_POSES:
+        raise ValueError(f"{name}: at most {_lib.WMVLM_MAX_POSES} poses (S * V), got {S} * {V}")
+    if not torch.is_tensor(P) or P.dtype != torch.float32 or P.dim() not in (2, 3) or P.shape[-1] != 3 \
+            or (P.dim() == 3 and P.shape[0] != V):
+        raise ValueError(f"{name}: the detector points must be float32 (N, 3), shared by the views, or ({V}, N, 3), "
+                         f"got {tuple(P.shape) if torch.is_tensor(P) else type(P).__name__} {getattr(P, 'dtype', '')}")
+    for what, t in (("xyz", xyz), ("reorient_v", reorient_v), ("detector points", P)):
+        if t.device != dev:
+            raise ValueError(f"{name}: {what} must live on the poses' device ({dev}), got {t.device}")
+    N = P.shape[-2]
+    return S, V, N, (3 * N if P.dim() == 3 else 0)
+
+
+def wmvlm_workspace(S, V, N, device):
+    """The (uninitialised) per-workgroup partial sums of :func:`wmvlm_normal_sums` for S starts seen from V views
+    with N rays: (S * V, ceil(N / 1024), 45) float64."""
+    n = int(_query_wmvlm("ddrr_wmvlm_workspace_bytes", int(S), int(V), int(N))) // 8
+    return torch.empty(n, dtype=torch.float64, device=device).view(S * V, -1, _lib.WMVLM_SUMS) if n else \
+        torch.empty(S * V, 0, _lib.WMVLM_SUMS, dtype=torch.float64, device=device)
+
+
+def _wmvlm_ws(name, ws, S, V, N):
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.dim() != 3 or ws.shape[-1] != _lib.WMVLM_SUMS \
+            or ws.numel() != wmvlm_workspace(S, V, N, "meta").numel():
+        raise ValueError(f"{name}: ws must be what wmvlm_workspace(S, V, N, device) returns")
+
+
+def wmvlm_raygen(rot, xyz, axes, reorient_v, Ainv, P, *, clear=None, clear_launch_ws=None):
+    """:func:`mvlm_raygen` with a detector per view (include/diffdrr_wmvlm_hip.h ddrr_wmvlm_raygen): pose
+    ``b = s * V + v`` is the Euler pose (rot[s], xyz[s]) with the reorient ``reorient_v[v]`` on the detector points
+    ``P[v]`` (``P`` (V, N, 3)) or ``P`` ((N, 3), shared by the views)
+    -> (Mw (S V, 3, 4), source_v (S V, 1, 3), target_v (S V, N, 3), img (S V, N)).  ``clear`` and ``clear_launch_ws``
+    as there."""
+    _require_gpu(rot)
+    S, V, N, P_stride = _wmvlm_views("wmvlm_raygen", rot, xyz, reorient_v, P)
+    B = S * V
+    rot, xyz, reorient_v, Ainv, P = (t.contiguous() for t in (rot, xyz, reorient_v, Ainv, P))
+    dev = rot.device
+    Mw = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
+    source = torch.empty(B, 1, 3, dtype=torch.float32, device=dev)
+    target = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+    img = torch.empty(B, N, dtype=torch.float32, device=dev)
+    if not _empty(B, N):
+        _launch_wmvlm("ddrr_wmvlm_raygen", dev, rot.data_ptr(), xyz.data_ptr(), *axes, reorient_v.data_ptr(),
+                      Ainv.data_ptr(), P.data_ptr(), P_stride, S, V, N, Mw.data_ptr(), source.data_ptr(),
+                      target.data_ptr(), img.data_ptr(), _ptr(clear), 0 if clear is None else clear.numel(),
+                      _ptr(clear_launch_ws))
+    elif clear is not None or clear_launch_ws is not None:
+        raise ValueError("wmvlm_raygen: nothing is launched for an empty batch, nothing is cleared")
+    return Mw, source, target, img
+
+
+def wmvlm_normal_sums(aux, fixed, weight, source, Mw, Ainv, P, rot, xyz, axes, reorient_v, *, eps=1e-8,
+                      with_img_path=True, ws=None, want_jacobian=False):
+    """The 45 weighted normal-equations sums of the S * V rendered poses from the brick kernel's blocked record
+    ``aux`` (include/diffdrr_wmvlm_hip.h ddrr_wmvlm_normal_sums; ``fixed`` (V, N) float32: one image per view;
+    ``weight`` ((1 | V), N) float32, >= 0 and finite -- not looked for here: one row shared by the views, or a row
+    per view; ``P`` (N, 3) or (V, N, 3); ``rot``, ``xyz`` (S, 3); ``reorient_v`` (V, 3, 4); the rest as
+    :func:`wmvlm_raygen` made them)
+    -> (ws (S V, G, 45) float64 per-workgroup partials, jac (S V, N, 6) float32 | None)."""
+    _require_gpu(rot)
+    S, V, N, P_stride = _wmvlm_views("wmvlm_normal_sums", rot, xyz, reorient_v, P)
+    B = S * V
+    dev = rot.device
+    if not torch.is_tensor(fixed) or fixed.shape != (V, N) or fixed.dtype != torch.float32:
+        raise ValueError(f"wmvlm_normal_sums: a float32 fixed image per view, ({V}, {N}), expected, got "
+                         f"{tuple(fixed.shape) if torch.is_tensor(fixed) else type(fixed).__name__} "
+                         f"{getattr(fixed, 'dtype', '')}")
+    if not torch.is_tensor(weight) or weight.dim() != 2 or weight.shape[0] not in (1, V) or weight.shape[1] != N \
+            or weight.dtype != torch.float32:
+        raise ValueError(f"wmvlm_normal_sums: a float32 weight of shape (1 | {V}, {N}) expected, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__} "
+                         f"{getattr(weight, 'dtype', '')}")
+    for what, t in (("fixed images", fixed), ("weight", weight)):
+        if t.device != dev:
+            raise ValueError(f"wmvlm_normal_sums: the {what} must live on the poses' device ({dev}), got {t.device}")
+    if Mw.shape[0] != B or source.shape[0] != B:
+        raise ValueError(f"wmvlm_normal_sums: Mw and source of {B} poses (S * V) expected, got {Mw.shape[0]} and "
+                         f"{source.shape[0]}")
+    fixed, weight, source = fixed.contiguous(), weight.contiguous(), source.contiguous()
+    Mw, Ainv, P, rot, xyz, reorient_v = (t.contiguous() for t in (Mw, Ainv, P, rot, xyz, reorient_v))
+    if ws is None:
+        ws = wmvlm_workspace(S, V, N, dev)
+    else:
+        _wmvlm_ws("wmvlm_normal_sums", ws, S, V, N)
+    jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
+    if B and N:
+        _launch_wmvlm("ddrr_wmvlm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), weight.data_ptr(),
+                      0 if weight.shape[0] == 1 else N, source.data_ptr(), Mw.data_ptr(), Ainv.data_ptr(),
+                      P.data_ptr(), P_stride, rot.data_ptr(), xyz.data_ptr(), *axes, reorient_v.data_ptr(), S, V, N,
+                      float(eps), int(bool(with_img_path)), ws.data_ptr(), _ptr(jac))
+    return ws, jac
+
+
+def wmvlm_step(ws, state, rot, xyz, V, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, damping_min=1e-7, damping_max=1e6,
+               out=None, ncc_views=None, sw_views=None):
+    """:func:`wlm_step` for S starts on the weighted sums of their V views (include/diffdrr_wmvlm_hip.h
+    ddrr_wmvlm_step): the non-empty views' normal equations are added, the mean of their NCC weighted by their sums
+    of weights is judged against ``state`` ((S, 40), :func:`lm_state`; column 37 takes the start's sum of weights),
+    the next trial is written into ``rot``, ``xyz`` (S, 3) IN PLACE -> the best such NCC per start (S,) float32.
+    ``ncc_views`` ((S, V) float32) and ``sw_views`` ((S, V) float64), both optional, receive the NCC and the sum of
+    weights of every view of the render just judged."""
+    _require_gpu(rot)
+    S, V = rot.shape[0], int(V)
+    if V < 1 or S * V > _lib.WMVLM_MAX_POSES:
+        raise ValueError(f"wmvlm_step: V >= 1 and at most {_lib.WMVLM_MAX_POSES} poses (S * V) expected, got "
+                         f"{S} * {V}")
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (S, 3):
+            raise ValueError("wmvlm_step: contiguous float32 (S, 3) pose parameters")
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (S, _lib.WMVLM_STATE_DOUBLES):
+        raise ValueError(f"wmvlm_step: state must be a contiguous float64 (S, {_lib.WMVLM_STATE_DOUBLES}) tensor")
+    _wmvlm_ws("wmvlm_step", ws, S, V, N)
+    for what, t in (("xyz", xyz), ("state", state), ("ws", ws)):
+        if t.device != rot.device:
+            raise ValueError(f"wmvlm_step: {what} must live on the poses' device ({rot.device}), got {t.device}")
+    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
+        raise ValueError("wmvlm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 "
+                         "expected")
+    for what, t, dtype in (("ncc_views", ncc_views, torch.float32), ("sw_views", sw_views, torch.float64)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.shape != (S, V)
+                              or t.device != rot.device):
+            raise ValueError(f"wmvlm_step: {what} must be a contiguous {str(dtype)[6:]} ({S}, {V}) tensor on the "
+                             "poses' device")
+    if out is None:
+        out = torch.empty(S, dtype=torch.float32, device=rot.device)
+    if S:
+        _launch_wmvlm("ddrr_wmvlm_step", rot.device, ws.data_ptr(), state.data_ptr(), rot.data_ptr(), xyz.data_ptr(),
+                      S, V, int(N), float(ncc_eps), float(up), float(down), float(damping_min), float(damping_max),
+                      out.data_ptr(), _ptr(ncc_views), _ptr(sw_views))
+    return out
+
+
 # ------------------------------------------------- weighted (masked) NCC (libdiffdrr_wncc_hip.so)
 def _launch_wncc(name, device, *args):
     """:func:`_launch` through the weighted NCC library."""

@@ -566,9 +566,10 @@ class MultiViewLevenbergMarquardt:
     (V, 4, 4) with the bottom row (0, 0, 0, 1) and an orthonormal rotation block; ``fixed`` float32 (V, 1, H, W) on
     the parameters' device, shared by the starts.  Anything else raises ``ValueError`` naming the condition.
 
-    Not built: pixel weights (``LevenbergMarquardt(weight=)`` has them for one view), a detector per view (all
-    views share the module's ``Detector``), the step as a captured HIP graph, and a fused multi-view ``DRR.ncc``
-    for a first-order loop (which renders ``view_poses(...)`` through the matrix route)."""
+    Not here: pixel weights and a detector per view -- ``WeightedMultiViewLevenbergMarquardt`` has both (this class
+    takes no ``weight`` and all its views share the module's ``Detector``).  Not built: the step as a captured HIP
+    graph, and a fused multi-view ``DRR.ncc`` for a first-order loop (which renders ``view_poses(...)`` through the
+    matrix route)."""
 
     def __init__(self, reg: Registration, fixed: torch.Tensor, views: torch.Tensor, damping: float = 1.0,
                  up: float = 4.0, down: float = 1.0 / 3.0, damping_min: float = 1e-7, damping_max: float = 1e6,
@@ -582,14 +583,14 @@ class MultiViewLevenbergMarquardt:
             float(up), float(down), float(damping_min), float(damping_max), float(eps))
         if not (self.up > 1.0 and 0.0 < self.down < 1.0 and 0.0 < self.damping_min <= self.damping_max < float("inf")
                 and self.damping_min <= float(damping) <= self.damping_max and self.eps >= 0.0):
-            raise ValueError("MultiViewLevenbergMarquardt: up > 1, 0 < down < 1, 0 < damping_min <= damping <= "
+            raise ValueError(f"{type(self).__name__}: up > 1, 0 < down < 1, 0 < damping_min <= damping <= "
                              "damping_max < inf and eps >= 0 expected")
         drr = reg.drr
         r, det = getattr(drr, "renderer", None), getattr(drr, "detector", None)
         rot, xyz = reg._rotation, reg._translation
 
         def refuse(what):
-            raise ValueError(f"MultiViewLevenbergMarquardt: {what}")
+            raise ValueError(f"{type(self).__name__}: {what}")
 
         if reg.parameterization != "euler_angles":
             refuse(f"parameterization must be 'euler_angles', not {reg.parameterization!r}")
@@ -648,10 +649,16 @@ class MultiViewLevenbergMarquardt:
         self.fixed = fixed.detach().reshape(V, H * W).contiguous()
         dev = rot.device
         self._state = ops.lm_state(S, damping, dev)
-        self._ws = ops.mvlm_workspace(S, V, self.N, dev)
+        self._ws = self._workspace(dev)
         self._aux = ops.brick_record_buffer(S * V, self.N, dev)
         self._view_ncc = torch.zeros(S, V, dtype=torch.float32, device=dev)
         self.steps_done = 0
+
+    def _workspace(self, device):
+        """the per-workgroup partial sums of a step (WeightedMultiViewLevenbergMarquardt has its own)"""
+        from . import ops
+
+        return ops.mvlm_workspace(self.S, self.V, self.N, device)
 
     # -- one render of the current parameters from every view with its record: the first two launches of a step
     def _render(self):
@@ -730,3 +737,190 @@ class MultiViewLevenbergMarquardt:
         """(S, V) float32: the NCC of every view of the render last judged, accepted or not (0 before the first
         step)."""
         return self._view_ncc.detach()
+
+
+# ------------------------------------------------------------------------- several views, weights, detectors
+def weighted_multiview_normal_equations_reference(J: torch.Tensor, x: torch.Tensor, f: torch.Tensor,
+                                                  w: torch.Tensor, eps: float = 1e-5):
+    """The definition of what a weighted multi-view Levenberg-Marquardt step solves, in float64 torch: the residual
+    of a start is the stack over its views of ``sqrt(w_v) (z_w(x_v) - z_w(f_v))``, every view the weighted problem of
+    :func:`weighted_normal_equations_reference` on its own, with ``J`` (S, V, N, 6) the derivative of ``x``
+    (S, V, N) with respect to the start's six parameters, ``f`` (V, N) one fixed image per view and ``w``
+    ((1 | V), N) one weight shared by the views or one per view
+    -> ``(ncc, A, g, ncc_views, sw_views)`` = ((S,), sum_v A_v (S, 6, 6), sum_v g_v (S, 6), ncc_v (S, V),
+    Sw_v (S, V)).  A view with ``Sw_v = 0`` is skipped (ncc_v 0, adds nothing).  The judged ``ncc`` is the mean of the
+    non-empty views' ncc_v weighted by Sw_v -- ``sum_v Sw_v (1 - ncc_v)`` is the objective, ``1/2 |r|^2`` up to
+    ``eps`` -- taken as ``sum_v (Sw_v ncc_v) / sum_v Sw_v`` over the non-empty views in ascending v; with exactly one
+    non-empty view it is that view's ncc_v itself, with none 0.  Scaling one view's weight by c makes that view count
+    c times; scaling every view's by c scales A and g by c and changes neither ncc nor the step.
+    ``ddrr_wmvlm_step`` forms the same (include/diffdrr_wmvlm_hip.h); this function is the yardstick of its tests."""
+    x = x.double()
+    ncc_v, A_v, g_v, sw_v = weighted_normal_equations_reference(J, x, f.double().expand(x.shape),
+                                                                w.double().expand(x.shape), eps)
+    S, V = ncc_v.shape
+    ncc = torch.zeros(S, dtype=torch.float64, device=x.device)
+    A = torch.zeros(S, 6, 6, dtype=torch.float64, device=x.device)
+    g = torch.zeros(S, 6, dtype=torch.float64, device=x.device)
+    for s in range(S):  # (in the order of the kernel: the first non-empty view initialises)
+        some = [v for v in range(V) if float(sw_v[s, v]) > 0]
+        if not some:
+            continue
+        C, Sw = sw_v[s, some[0]] * ncc_v[s, some[0]], sw_v[s, some[0]]
+        A[s], g[s] = A_v[s, some[0]], g_v[s, some[0]]
+        for v in some[1:]:
+            C, Sw = C + sw_v[s, v] * ncc_v[s, v], Sw + sw_v[s, v]
+            A[s], g[s] = A[s] + A_v[s, v], g[s] + g_v[s, v]
+        ncc[s] = ncc_v[s, some[0]] if len(some) == 1 else C / Sw
+    return ncc, A, g, ncc_v, sw_v
+
+
+class WeightedMultiViewLevenbergMarquardt(MultiViewLevenbergMarquardt):
+    """``MultiViewLevenbergMarquardt`` with a pixel weight and a detector per view: what a real biplane acquisition
+    needs at once -- every plane has its own collimator border and its own instruments in view, and frontal and
+    lateral planes rarely share source-detector distance, pixel pitch or principal point.
+
+        lm = WeightedMultiViewLevenbergMarquardt(reg, fixed, K, weight=w, detectors=(None, lateral))
+        for _ in range(30):
+            ncc = lm.step()          # (S,) best weighted NCC over the views so far
+        lm.commit()
+
+    The objective of a start is ``sum_v 1/2 sum_n w_vn (z_w(drr_v)_n - z_w(fixed_v)_n)^2 = sum_v Sw_v (1 - ncc_v)``
+    up to ``eps``: per view the weighted problem of ``LevenbergMarquardt(weight=)``, the residuals stacked.  A pixel
+    of weight 1 counts the same in every view; scaling ONE view's weight by c makes that view count c times (a
+    per-view confidence); scaling all views' by c changes nothing.  The NCC that is judged, returned and kept as
+    ``best_ncc`` is the mean of the views' NCC weighted by their sums of weights, the objective the step minimises
+    (not the plain mean).  A view whose weights are all 0 is skipped; a start all of whose views are empty never
+    moves and reports 0.
+
+    ``weight``: float32 ((1 | V), 1, H, W) on the parameters' device, finite and >= 0 (checked once, here; then read
+    in place at every step, as ``fixed`` is); one image shared by the views, or one per view; ``None``: ones, shared.
+    Pixels of weight 0 are selected out of every sum: ``fixed`` may hold anything there.  Editing the weight between
+    steps makes "best so far" compare different objectives: build a new object instead.
+
+    ``detectors``: ``None``, or a sequence of V entries, each a ``Detector`` or ``None`` (the module's own).  Every
+    detector must have the module's ``height x width`` and no ``n_subsample``; view v then renders the calibrated
+    points ``det_v.calibration(det_v.full_target())[0]`` with ``(views[v] @ det_v._reorient)[:3]``.  ``None`` for
+    all views keeps one set of points for all of them.
+
+    ``step()`` is four launches and no host synchronisation: ``ddrr_wmvlm_raygen`` with the clears, the brick kernel
+    with its record and no image (S * V poses), ``ddrr_wmvlm_normal_sums`` and ``ddrr_wmvlm_step``
+    (include/diffdrr_wmvlm_hip.h).  ``view_ncc`` (S, V) and ``view_weight_sum`` (S, V) float64 hold the NCC and the
+    sum of weights of every view of the render last judged, ``weight_sum`` (S,) their sum over the views;
+    ``commit``, ``damping``, ``best_parameters``, ``best_ncc``, ``accepted`` and ``jacobian()`` ((S, V, N, 6)) are
+    the parent's.  Domain and refusals: the parent's.
+
+    Not built: weights per start (one weight image per view serves all starts), the step as a captured HIP graph,
+    and a fused multi-view ``DRR.ncc`` for a first-order loop."""
+
+    def __init__(self, reg: Registration, fixed: torch.Tensor, views: torch.Tensor,
+                 weight: torch.Tensor | None = None, detectors=None, damping: float = 1.0, up: float = 4.0,
+                 down: float = 1.0 / 3.0, damping_min: float = 1e-7, damping_max: float = 1e6, eps: float = 1e-5):
+        from .detector import Detector
+
+        super().__init__(reg, fixed, views, damping=damping, up=up, down=down, damping_min=damping_min,
+                         damping_max=damping_max, eps=eps)
+        V, N = self.V, self.N
+        det = reg.drr.detector
+        H, W = det.height, det.width
+        dev = reg._rotation.device
+
+        def refuse(what):
+            raise ValueError(f"WeightedMultiViewLevenbergMarquardt: {what}")
+
+        if weight is None:
+            weight = torch.ones(1, 1, H, W, dtype=torch.float32, device=dev)
+        if not torch.is_tensor(weight) or weight.dtype != torch.float32:
+            refuse(f"weight must be a float32 tensor, got {getattr(weight, 'dtype', type(weight).__name__)}")
+        if weight.dim() != 4 or weight.shape[0] not in (1, V) or tuple(weight.shape[1:]) != (1, H, W):
+            refuse(f"weight must have the shape ((1 | {V}), 1, {H}, {W}), got {tuple(weight.shape)}")
+        if weight.device != dev:
+            refuse(f"weight must live on the parameters' device ({dev}), got {weight.device}")
+        if not bool(torch.isfinite(weight).all()):
+            refuse("weight must be finite (it holds NaN or Inf)")
+        if bool((weight < 0).any()):
+            refuse("weight must not be negative")
+        # (a view where the caller's tensor is contiguous: read in place, as the fixed image is)
+        self.weight = weight.detach().reshape(weight.shape[0], N).contiguous()
+        self._P = None  # (None: the module's own calibrated points, one set for all views)
+        if detectors is not None:
+            if isinstance(detectors, (Detector, torch.Tensor, str)) or not hasattr(detectors, "__len__") \
+                    or len(detectors) != V:
+                refuse(f"detectors must be a sequence of {V} entries (one per view), each a Detector or None")
+            dets = [det if d is None else d for d in detectors]
+            for v, d in enumerate(dets):
+                if not isinstance(d, Detector):
+                    refuse(f"detectors[{v}] must be a Detector or None, got {type(d).__name__}")
+                if (d.height, d.width) != (H, W):
+                    refuse(f"detectors[{v}] must have the module's height x width ({H} x {W}), got "
+                           f"{d.height} x {d.width}")
+                if d.n_subsample is not None:
+                    refuse(f"detectors[{v}] must be dense (n_subsample must be None)")
+            if any(d is not det for d in dets):
+                with torch.no_grad():
+                    self._P = torch.stack([d.calibration(d.full_target())[0].detach().to(dev, torch.float32)
+                                           for d in dets]).contiguous()
+                    Ro = torch.stack([self.views[v] @ d._reorient.detach().to(self.views) for v, d in enumerate(dets)])
+                    self._reorient_v = Ro[:, :3, :].to(torch.float32).contiguous()
+        self._view_sw = torch.zeros(self.S, V, dtype=torch.float64, device=dev)
+
+    def _workspace(self, device):
+        from . import ops
+
+        return ops.wmvlm_workspace(self.S, self.V, self.N, device)
+
+    def _render(self):
+        from . import ops
+        from .renderers import _brick_axis, _brick_storage
+
+        drr = self.reg.drr
+        rot, xyz = self.reg._rotation.detach(), self.reg._translation.detach()
+        rot, _, P, Ainv, axes, cfg = drr._euler_args(rot, self.reg.convention, False)
+        if self._P is not None:
+            P = self._P
+        B, volume = self.S * self.V, drr.density
+        launch_ws = ops.launch_workspace(volume.shape, volume.device)
+        Mw, source, target, img = ops.wmvlm_raygen(rot, xyz, axes, self._reorient_v, Ainv, P, clear=self._aux,
+                                                   clear_launch_ws=launch_ws)
+        ops.siddon_forward_bricks(
+            volume, source, target, img, cfg["det"], voxel_shift=cfg["voxel_shift"], eps=cfg["eps"], want_aux=True,
+            storage=_brick_storage(volume, cfg, B), axis=_brick_axis(volume, cfg, B), want_image=False, aux=self._aux,
+            launch_ws=launch_ws, cleared=True)
+        return dict(aux=self._aux, source=source, Mw=Mw, Ainv=Ainv, P=P, rot=rot, xyz=xyz, axes=axes,
+                    reorient_v=self._reorient_v), dict(eps=cfg["eps"], with_img_path=not cfg["stop_gradients"])
+
+    @torch.no_grad()
+    def step(self) -> torch.Tensor:
+        """Render the current parameters from every view, accept or reject them, write the next trial into them
+        -> the best NCC (the views' weighted by their sums of weights) per start so far, (S,), detached."""
+        from . import ops
+
+        args, kw = self._render()
+        ops.wmvlm_normal_sums(args.pop("aux"), self.fixed, self.weight, **args, **kw, ws=self._ws)
+        out = ops.wmvlm_step(self._ws, self._state, args["rot"], args["xyz"], self.V, self.N, ncc_eps=self.eps,
+                             up=self.up, down=self.down, damping_min=self.damping_min, damping_max=self.damping_max,
+                             ncc_views=self._view_ncc, sw_views=self._view_sw)
+        self.steps_done += 1
+        return out
+
+    @torch.no_grad()
+    def jacobian(self) -> torch.Tensor:
+        """d image_v / d (rot, xyz) at the current parameters, (S, V, N, 6) float32, for every pixel whatever its
+        weight: one render and ``ddrr_wmvlm_normal_sums`` with its per-ray output.  The optimiser's state is not
+        touched."""
+        from . import ops
+
+        args, kw = self._render()
+        jac = ops.wmvlm_normal_sums(args.pop("aux"), self.fixed, self.weight, **args, **kw, want_jacobian=True)[1]
+        return jac.view(self.S, self.V, self.N, 6)
+
+    @property
+    def view_weight_sum(self) -> torch.Tensor:
+        """(S, V) float64: the sum of the weights of every view of the render last judged (0 before the first
+        step)."""
+        return self._view_sw.detach()
+
+    @property
+    def weight_sum(self) -> torch.Tensor:
+        """(S,) float64: the sum of the weights over the views of the render last judged (0 before the first
+        step)."""
+        return self._state[:, 37].detach()
