@@ -1,9 +1,13 @@
 // lm_core.h -- the arithmetic of the Levenberg-Marquardt kernels (lm.hip; include/diffdrr_lm_hip.h has
 // the definitions): a ray's pose Jacobian row from the brick kernel's backward record, the products it
 // adds to the 44 sums of the normal equations, and the accept / reject / solve step on those sums.
-// Host and device (DDRR_HD): tests/emu/lm_emu.cpp compiles the same functions for the CPU.
+// Host and device (DDRR_HD): tests/emu/lm_emu.cpp compiles the same functions for the CPU.  The argument checks of
+// the single-view entries (lm.hip, wlm.hip) are here too, each condition once.
 // The ray and pose derivatives are siddon_core.h's and raygen_core.h's own functions, composed.
 #pragma once
+
+#include <math.h>
+#include <stdint.h>
 
 #include "../../include/diffdrr_lm_hip.h"
 #include "raygen_core.h"
@@ -78,6 +82,16 @@ DDRR_HD double slice_sum(const float *u, int count, int k, int slice) {
     }
     return v;
 }
+
+// What lm_kernels.h's normal-sums body is written on: how many sums a workgroup takes and one (sum, slice) of them
+// from the staged rows (wlm_core.h has the weighted one, which reads the plane of weights `w` as well).
+struct PlainSums {
+    static constexpr bool kWeighted = false;
+    static constexpr int kCount = kSums;
+    DDRR_HD static double slice(const float *u, const float *, int count, int k, int sl) {
+        return slice_sum(u, count, k, sl);
+    }
+};
 
 // ncc, A (upper triangle) and g of the residual z(x) - z(f) from the 44 sums: step 1 of ddrr_lm_step, with n
 // the number of rays (wlm_core.h: the sum of their weights, every sum weighted)
@@ -187,6 +201,48 @@ DDRR_HD void step_pose(const double *S, int N, double ncc_eps, double up, double
     double ncc, A[21], g[6];
     normal_equations(S, N, ncc_eps, ncc, A, g);
     judge_and_solve(ncc, A, g, up, down, lambda_min, lambda_max, st, rot, xyz, ncc_out);
+}
+
+// What both builds check before anything runs -> the message, or nullptr.  `own` is the message of a condition of
+// the caller's own (wlm_core.h's weight stride): it is reported where that condition stands in the caller's order.
+inline const char *check_axes(int a0, int a1, int a2) {
+    if (a0 < 0 || a0 > 2 || a1 < 0 || a1 > 2 || a2 < 0 || a2 > 2 || a1 == a0 || a1 == a2)
+        return "invalid Euler convention";
+    return nullptr;
+}
+
+inline const char *check_hyper(double ncc_eps, double up, double down, double lambda_min, double lambda_max) {
+    if (!(ncc_eps >= 0.0 && isfinite(ncc_eps))) return "ncc_eps must be >= 0 and finite";
+    if (!(up > 1.0 && isfinite(up) && down > 0.0 && down < 1.0)) return "up must be > 1 and finite, down in (0, 1)";
+    if (!(lambda_min > 0.0 && lambda_min <= lambda_max && isfinite(lambda_max)))
+        return "0 < lambda_min <= lambda_max, finite, expected";
+    return nullptr;
+}
+
+inline const char *check_sums_args(const void *aux, const void *x1, long x1_stride, const void *source_v,
+                                   const void *Mw, const void *Ainv, const void *P, const void *rot, const void *xyz,
+                                   int a0, int a1, int a2, const void *reorient34, int B, int N, const void *ws,
+                                   const char *own = nullptr) {
+    if (!aux || !x1 || !source_v || !Mw || !Ainv || !P || !rot || !xyz || !reorient34 || !ws) return "null pointer";
+    if (const char *bad = check_axes(a0, a1, a2)) return bad;
+    if (B < 0 || N < 1) return "bad batch / image size";
+    if (x1_stride != 0 && x1_stride != N) return "x1_stride must be N, or 0 for a shared image";
+    if (own) return own;
+    if (reinterpret_cast<uintptr_t>(ws) & 7) return "ws must be 8-byte aligned";
+    if (B > DDRR_LM_MAX_POSES) return "at most 65535 poses per call";
+    return nullptr;
+}
+
+inline const char *check_step_args(const void *ws, const void *state, const void *rot, const void *xyz, int B, int N,
+                                   double ncc_eps, double up, double down, double lambda_min, double lambda_max,
+                                   const void *ncc_out) {
+    if (!ws || !state || !rot || !xyz || !ncc_out) return "null pointer";
+    if (B < 0 || N < 1) return "bad batch / image size";
+    if (const char *bad = check_hyper(ncc_eps, up, down, lambda_min, lambda_max)) return bad;
+    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(state)) & 7)
+        return "ws and state must be 8-byte aligned";
+    if (B > DDRR_LM_MAX_POSES) return "at most 65535 poses per call";
+    return nullptr;
 }
 
 }  // namespace ddrr_lm

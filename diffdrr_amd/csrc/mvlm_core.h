@@ -45,26 +45,22 @@ DDRR_HD void step_start(const double *acc, int V, double up, double down, double
 
 inline int groups_of(int N) { return (N + kGroupRays - 1) / kGroupRays; }
 
-// what both builds check before anything runs -> the message, or nullptr
+// What both builds check before anything runs -> the message, or nullptr.  `own` is the message of a condition of
+// the caller's own (wmvlm_core.h's strides): it is reported where that condition stands in the caller's order.
 inline const char *check_shape(int S, int V, int N) {
     if (S < 0 || V < 1 || N < 1) return "bad batch / view count / image size (S >= 0, V >= 1, N >= 1)";
     if ((long)S * V > DDRR_MVLM_MAX_POSES) return "at most 65535 poses (S * V) per call";
     return nullptr;
 }
 
-inline const char *check_axes(int a0, int a1, int a2) {
-    if (a0 < 0 || a0 > 2 || a1 < 0 || a1 > 2 || a2 < 0 || a2 > 2 || a1 == a0 || a1 == a2)
-        return "invalid Euler convention";
-    return nullptr;
-}
-
 inline const char *check_raygen_args(const void *rot, const void *xyz, int a0, int a1, int a2, const void *reorient_v,
                                      const void *Ainv, const void *P, int S, int V, int N, const void *Mw,
                                      const void *source_v, const void *target_v, const void *img, const void *clear,
-                                     long clear_floats, const void *clear_launch_ws) {
+                                     long clear_floats, const void *clear_launch_ws, const char *own = nullptr) {
     if (!rot || !xyz || !reorient_v || !Ainv || !P || !Mw || !source_v || !target_v || !img) return "null pointer";
     if (const char *bad = check_axes(a0, a1, a2)) return bad;
     if (const char *bad = check_shape(S, V, N)) return bad;
+    if (own) return own;
     if (clear_floats < 0 || (clear_floats > 0 && !clear)) return "clear_floats without a buffer";
     if ((reinterpret_cast<uintptr_t>(clear) & 15) || (reinterpret_cast<uintptr_t>(clear_launch_ws) & 15))
         return "the buffers to clear must be 16-byte aligned";
@@ -75,23 +71,31 @@ inline const char *check_raygen_args(const void *rot, const void *xyz, int a0, i
 
 inline const char *check_sums_args(const void *aux, const void *x1, const void *source_v, const void *Mw,
                                    const void *Ainv, const void *P, const void *rot, const void *xyz, int a0, int a1,
-                                   int a2, const void *reorient_v, int S, int V, int N, const void *ws) {
+                                   int a2, const void *reorient_v, int S, int V, int N, const void *ws,
+                                   const char *own = nullptr) {
     if (!aux || !x1 || !source_v || !Mw || !Ainv || !P || !rot || !xyz || !reorient_v || !ws) return "null pointer";
     if (const char *bad = check_axes(a0, a1, a2)) return bad;
     if (const char *bad = check_shape(S, V, N)) return bad;
+    if (own) return own;
     if (reinterpret_cast<uintptr_t>(ws) & 7) return "ws must be 8-byte aligned";
     return nullptr;
+}
+
+// (the step's conditions but the alignment, whose message names the pointers of the entry)
+inline const char *check_step_values(const void *ws, const void *state, const void *rot, const void *xyz, int S,
+                                     int V, int N, double ncc_eps, double up, double down, double lambda_min,
+                                     double lambda_max, const void *ncc_out) {
+    if (!ws || !state || !rot || !xyz || !ncc_out) return "null pointer";
+    if (const char *bad = check_shape(S, V, N)) return bad;
+    return check_hyper(ncc_eps, up, down, lambda_min, lambda_max);
 }
 
 inline const char *check_step_args(const void *ws, const void *state, const void *rot, const void *xyz, int S, int V,
                                    int N, double ncc_eps, double up, double down, double lambda_min,
                                    double lambda_max, const void *ncc_out) {
-    if (!ws || !state || !rot || !xyz || !ncc_out) return "null pointer";
-    if (const char *bad = check_shape(S, V, N)) return bad;
-    if (!(ncc_eps >= 0.0 && isfinite(ncc_eps))) return "ncc_eps must be >= 0 and finite";
-    if (!(up > 1.0 && isfinite(up) && down > 0.0 && down < 1.0)) return "up must be > 1 and finite, down in (0, 1)";
-    if (!(lambda_min > 0.0 && lambda_min <= lambda_max && isfinite(lambda_max)))
-        return "0 < lambda_min <= lambda_max, finite, expected";
+    if (const char *bad = check_step_values(ws, state, rot, xyz, S, V, N, ncc_eps, up, down, lambda_min, lambda_max,
+                                            ncc_out))
+        return bad;
     if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(state)) & 7)
         return "ws and state must be 8-byte aligned";
     return nullptr;

@@ -16,8 +16,8 @@ namespace ddrr_wlm {
 using namespace ddrr_lm;
 
 static_assert(DDRR_WLM_SUMS == DDRR_LM_SUMS + 1 && DDRR_WLM_GROUP_RAYS == DDRR_LM_GROUP_RAYS &&
-                  DDRR_WLM_STATE_DOUBLES == DDRR_LM_STATE_DOUBLES,
-              "the weighted sums are the 44 of lm_core.h and sum w, on its launch shape and state");
+                  DDRR_WLM_STATE_DOUBLES == DDRR_LM_STATE_DOUBLES && DDRR_WLM_MAX_POSES == DDRR_LM_MAX_POSES,
+              "the weighted sums are the 44 of lm_core.h and sum w, on its launch shape, state and pose cap");
 
 constexpr int kWSums = DDRR_WLM_SUMS;
 constexpr int kSumW = DDRR_LM_SUMS;  // [44] = sum w
@@ -65,37 +65,25 @@ DDRR_HD void wstep_pose(const double *S, double ncc_eps, double up, double down,
     judge_and_solve(ncc, A, g, up, down, lambda_min, lambda_max, st, rot, xyz, ncc_out);
 }
 
-// what both builds check before anything runs -> the message, or nullptr
+// lm_core.h's PlainSums for the 45 weighted sums: `w` is the plane of weights with the constant 1 behind it
+struct WeightedSums {
+    static constexpr bool kWeighted = true;
+    static constexpr int kCount = kWSums;
+    DDRR_HD static double slice(const float *u, const float *w, int count, int k, int sl) {
+        return wslice_sum(u, w, w + kGroupRays, count, k, sl);
+    }
+};
+
+// what both builds check before anything runs -> the message, or nullptr: lm_core.h's conditions with the weight's
+// (the step's are lm_core.h's check_step_args as they stand)
 inline const char *check_sums_args(const void *aux, const void *x1, long x1_stride, const void *w, long w_stride,
                                    const void *source_v, const void *Mw, const void *Ainv, const void *P,
                                    const void *rot, const void *xyz, int a0, int a1, int a2, const void *reorient34,
                                    int B, int N, const void *ws) {
-    if (!aux || !x1 || !w || !source_v || !Mw || !Ainv || !P || !rot || !xyz || !reorient34 || !ws)
-        return "null pointer";
-    if (a0 < 0 || a0 > 2 || a1 < 0 || a1 > 2 || a2 < 0 || a2 > 2 || a1 == a0 || a1 == a2)
-        return "invalid Euler convention";
-    if (B < 0 || N < 1) return "bad batch / image size";
-    if (x1_stride != 0 && x1_stride != N) return "x1_stride must be N, or 0 for a shared image";
-    if (w_stride != 0 && w_stride != N) return "w_stride must be N, or 0 for a shared weight";
-    if (reinterpret_cast<uintptr_t>(ws) & 7) return "ws must be 8-byte aligned";
-    if (B > DDRR_WLM_MAX_POSES) return "at most 65535 poses per call";
-    return nullptr;
-}
-
-inline const char *check_step_args(const void *ws, const void *state, const void *rot, const void *xyz, int B, int N,
-                                   double ncc_eps, double up, double down, double lambda_min, double lambda_max,
-                                   const void *ncc_out) {
-    if (!ws || !state || !rot || !xyz || !ncc_out) return "null pointer";
-    if (B < 0 || N < 1) return "bad batch / image size";
-    if (!(ncc_eps >= 0.0 && isfinite(ncc_eps))) return "ncc_eps must be >= 0 and finite";
-    if (!(up > 1.0 && isfinite(up) && down > 0.0 && down < 1.0))
-        return "up must be > 1 and finite, down in (0, 1)";
-    if (!(lambda_min > 0.0 && lambda_min <= lambda_max && isfinite(lambda_max)))
-        return "0 < lambda_min <= lambda_max, finite, expected";
-    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(state)) & 7)
-        return "ws and state must be 8-byte aligned";
-    if (B > DDRR_WLM_MAX_POSES) return "at most 65535 poses per call";
-    return nullptr;
+    if (!w) return "null pointer";
+    return ddrr_lm::check_sums_args(
+        aux, x1, x1_stride, source_v, Mw, Ainv, P, rot, xyz, a0, a1, a2, reorient34, B, N, ws,
+        w_stride != 0 && w_stride != N ? "w_stride must be N, or 0 for a shared weight" : nullptr);
 }
 
 }  // namespace ddrr_wlm

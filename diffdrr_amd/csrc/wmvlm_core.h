@@ -11,7 +11,10 @@
 #include <stdint.h>
 
 #include "../../include/diffdrr_wmvlm_hip.h"
+#include "mvlm_core.h"
 #include "wlm_core.h"
+
+static_assert(DDRR_WMVLM_MAX_POSES == DDRR_MVLM_MAX_POSES, "mvlm_core.h's check_shape holds for this library");
 
 namespace ddrr_wmvlm {
 
@@ -73,18 +76,9 @@ DDRR_HD void wstep_start(const double *acc, double up, double down, double lambd
 
 inline int groups_of(int N) { return (N + kGroupRays - 1) / kGroupRays; }
 
-// what both builds check before anything runs -> the message, or nullptr
-inline const char *check_shape(int S, int V, int N) {
-    if (S < 0 || V < 1 || N < 1) return "bad batch / view count / image size (S >= 0, V >= 1, N >= 1)";
-    if ((long)S * V > DDRR_WMVLM_MAX_POSES) return "at most 65535 poses (S * V) per call";
-    return nullptr;
-}
-
-inline const char *check_axes(int a0, int a1, int a2) {
-    if (a0 < 0 || a0 > 2 || a1 < 0 || a1 > 2 || a2 < 0 || a2 > 2 || a1 == a0 || a1 == a2)
-        return "invalid Euler convention";
-    return nullptr;
-}
+// what both builds check before anything runs -> the message, or nullptr: mvlm_core.h's conditions with the strides
+// of the weight and the detector points (in their place after the shape) and with sw_views in the step's alignment
+using ddrr_mvlm::check_shape;
 
 inline const char *check_strides(long w_stride, long P_stride, int N) {
     if (w_stride != 0 && w_stride != N) return "w_stride must be N, or 0 for a weight shared by the views";
@@ -96,40 +90,25 @@ inline const char *check_raygen_args(const void *rot, const void *xyz, int a0, i
                                      const void *Ainv, const void *P, long P_stride, int S, int V, int N,
                                      const void *Mw, const void *source_v, const void *target_v, const void *img,
                                      const void *clear, long clear_floats, const void *clear_launch_ws) {
-    if (!rot || !xyz || !reorient_v || !Ainv || !P || !Mw || !source_v || !target_v || !img) return "null pointer";
-    if (const char *bad = check_axes(a0, a1, a2)) return bad;
-    if (const char *bad = check_shape(S, V, N)) return bad;
-    if (const char *bad = check_strides(0, P_stride, N)) return bad;
-    if (clear_floats < 0 || (clear_floats > 0 && !clear)) return "clear_floats without a buffer";
-    if ((reinterpret_cast<uintptr_t>(clear) & 15) || (reinterpret_cast<uintptr_t>(clear_launch_ws) & 15))
-        return "the buffers to clear must be 16-byte aligned";
-    if ((clear_floats > 0 || clear_launch_ws) && S == 0)
-        return "nothing is launched for an empty batch: clear the buffers yourself";
-    return nullptr;
+    return ddrr_mvlm::check_raygen_args(rot, xyz, a0, a1, a2, reorient_v, Ainv, P, S, V, N, Mw, source_v, target_v, img,
+                                        clear, clear_floats, clear_launch_ws, check_strides(0, P_stride, N));
 }
 
 inline const char *check_sums_args(const void *aux, const void *x1, const void *w, long w_stride,
                                    const void *source_v, const void *Mw, const void *Ainv, const void *P,
                                    long P_stride, const void *rot, const void *xyz, int a0, int a1, int a2,
                                    const void *reorient_v, int S, int V, int N, const void *ws) {
-    if (!aux || !x1 || !w || !source_v || !Mw || !Ainv || !P || !rot || !xyz || !reorient_v || !ws)
-        return "null pointer";
-    if (const char *bad = check_axes(a0, a1, a2)) return bad;
-    if (const char *bad = check_shape(S, V, N)) return bad;
-    if (const char *bad = check_strides(w_stride, P_stride, N)) return bad;
-    if (reinterpret_cast<uintptr_t>(ws) & 7) return "ws must be 8-byte aligned";
-    return nullptr;
+    if (!w) return "null pointer";
+    return ddrr_mvlm::check_sums_args(aux, x1, source_v, Mw, Ainv, P, rot, xyz, a0, a1, a2, reorient_v, S, V, N, ws,
+                                      check_strides(w_stride, P_stride, N));
 }
 
 inline const char *check_step_args(const void *ws, const void *state, const void *rot, const void *xyz, int S, int V,
                                    int N, double ncc_eps, double up, double down, double lambda_min,
                                    double lambda_max, const void *ncc_out, const void *sw_views) {
-    if (!ws || !state || !rot || !xyz || !ncc_out) return "null pointer";
-    if (const char *bad = check_shape(S, V, N)) return bad;
-    if (!(ncc_eps >= 0.0 && isfinite(ncc_eps))) return "ncc_eps must be >= 0 and finite";
-    if (!(up > 1.0 && isfinite(up) && down > 0.0 && down < 1.0)) return "up must be > 1 and finite, down in (0, 1)";
-    if (!(lambda_min > 0.0 && lambda_min <= lambda_max && isfinite(lambda_max)))
-        return "0 < lambda_min <= lambda_max, finite, expected";
+    if (const char *bad = ddrr_mvlm::check_step_values(ws, state, rot, xyz, S, V, N, ncc_eps, up, down, lambda_min,
+                                                       lambda_max, ncc_out))
+        return bad;
     if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(sw_views)) &
         7)
         return "ws, state and sw_views must be 8-byte aligned";

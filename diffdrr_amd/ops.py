@@ -1723,6 +1723,110 @@ def fbp_backproject(images, views, volume_shape=None, *, distance_weight=False, 
     return out
 
 
+# ------------------------------------------------- Levenberg-Marquardt registration: what the four libraries share
+def _lm_workspace(nbytes, poses, sums, device):
+    """The (uninitialised) (poses, G, sums) float64 partial sums of ``nbytes`` bytes, as a library's query sized it."""
+    n = int(nbytes) // 8
+    return torch.empty(n, dtype=torch.float64, device=device).view(poses, -1, sums) if n else \
+        torch.empty(poses, 0, sums, dtype=torch.float64, device=device)
+
+
+def _check_lm_ws(name, ws, workspace, *shape, sums=None):
+    """``ws`` is what ``workspace(*shape, device)`` (the family's ``<family>_workspace``, ``name`` being
+    ``<family>_<entry>``) returns, as far as every family looks; with ``sums`` (wmvlm's own look) its three axes and
+    the last of them too"""
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != workspace(*shape, "meta").numel() \
+            or (sums is not None and (ws.dim() != 3 or ws.shape[-1] != sums)):
+        raise ValueError(f"{name}: ws must be what {name.split('_')[0]}_workspace("
+                         f"{'B, N' if len(shape) == 2 else 'S, V, N'}, device) returns")
+
+
+def _check_lm_image(name, t, what, rows, N):
+    """``t`` (the fixed image or the weight) is a float32 (r, N) tensor with r one of ``rows``: (1, B) for one row
+    shared by the B poses or one each, (V,) for one per view"""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] not in rows or t.shape[1] != N or t.dtype != torch.float32:
+        expected = f"of shape (1 | {rows[1]}, {N})" if len(rows) == 2 else f"per view, ({rows[0]}, {N}),"
+        raise ValueError(f"{name}: a float32 {what} {expected} expected, got "
+                         f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__} {getattr(t, 'dtype', '')}")
+
+
+def _check_lm_devices(name, dev, *named):
+    for what, t in named:
+        if t.device != dev:
+            raise ValueError(f"{name}: {what} must live on the poses' device ({dev}), got {t.device}")
+
+
+def _check_lm_state(name, rot, xyz, state, B="B"):
+    """the step's own tensors: (B, 3) parameters, written in place, and the (B, 40) state"""
+    n = rot.shape[0]
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, 3):
+            raise ValueError(f"{name}: contiguous float32 ({B}, 3) pose parameters")
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (n, _lib.LM_STATE_DOUBLES):
+        raise ValueError(f"{name}: state must be a contiguous float64 ({B}, {_lib.LM_STATE_DOUBLES}) tensor")
+
+
+def _check_lm_hyper(name, ncc_eps, up, down, damping_min, damping_max):
+    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
+        raise ValueError(f"{name}: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
+
+
+def _check_lm_views_out(name, S, V, dev, **outs):
+    """the optional per-view outputs of a multi-view step: (tensor, dtype) by name"""
+    for what, (t, dtype) in outs.items():
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.shape != (S, V) or t.device != dev):
+            raise ValueError(f"{name}: {what} must be a contiguous {str(dtype)[6:]} ({S}, {V}) tensor on the poses' "
+                             "device")
+
+
+def _lm_views(name, rot, xyz, reorient_v, *P, max_poses=_lib.MVLM_MAX_POSES):
+    """(S, V) of (S, 3) parameters and (V, 3, 4) float32 reorients; given the detector points ``P`` -- (N, 3) shared
+    by the views (stride 0) or (V, N, 3) (stride 3 N) -- (S, V, N, P_stride), everything on the poses' device;
+    refuses what the entries would misread."""
+    S = rot.shape[0]
+    for t in (rot, xyz):
+        if t.dtype != torch.float32 or t.shape != (S, 3):
+            raise ValueError(f"{name}: float32 (S, 3) pose parameters expected, got {tuple(t.shape)} {t.dtype}")
+    if reorient_v.dim() != 3 or reorient_v.shape[0] < 1 or tuple(reorient_v.shape[1:]) != (3, 4) \
+            or reorient_v.dtype != torch.float32:
+        raise ValueError(f"{name}: reorient_v must be a float32 (V, 3, 4) tensor with V >= 1, got "
+                         f"{tuple(reorient_v.shape)} {reorient_v.dtype}")
+    V = reorient_v.shape[0]
+    if S * V > max_poses:
+        raise ValueError(f"{name}: at most {max_poses} poses (S * V), got {S} * {V}")
+    if not P:
+        return S, V
+    P, = P
+    if not torch.is_tensor(P) or P.dtype != torch.float32 or P.dim() not in (2, 3) or P.shape[-1] != 3 \
+            or (P.dim() == 3 and P.shape[0] != V):
+        raise ValueError(f"{name}: the detector points must be float32 (N, 3), shared by the views, or ({V}, N, 3), "
+                         f"got {tuple(P.shape) if torch.is_tensor(P) else type(P).__name__} {getattr(P, 'dtype', '')}")
+    for what, t in (("xyz", xyz), ("reorient_v", reorient_v), ("detector points", P)):
+        if t.device != rot.device:
+            raise ValueError(f"{name}: {what} must live on the poses' device ({rot.device}), got {t.device}")
+    N = P.shape[-2]
+    return S, V, N, (3 * N if P.dim() == 3 else 0)
+
+
+def _lm_raygen(name, launch, rot, xyz, axes, reorient_v, Ainv, P, P_stride, S, V, N, clear, clear_launch_ws):
+    """The multi-view ray generation ``ddrr_<name>`` (``P_stride``: the run of arguments behind ``P``, () or (stride,))
+    -> (Mw (S V, 3, 4), source_v (S V, 1, 3), target_v (S V, N, 3), img (S V, N))"""
+    B = S * V
+    rot, xyz, reorient_v, Ainv, P = (t.contiguous() for t in (rot, xyz, reorient_v, Ainv, P))
+    dev = rot.device
+    Mw = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
+    source = torch.empty(B, 1, 3, dtype=torch.float32, device=dev)
+    target = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+    img = torch.empty(B, N, dtype=torch.float32, device=dev)
+    if not _empty(B, N):
+        launch("ddrr_" + name, dev, rot.data_ptr(), xyz.data_ptr(), *axes, reorient_v.data_ptr(), Ainv.data_ptr(),
+               P.data_ptr(), *P_stride, S, V, N, Mw.data_ptr(), source.data_ptr(), target.data_ptr(), img.data_ptr(),
+               _ptr(clear), 0 if clear is None else clear.numel(), _ptr(clear_launch_ws))
+    elif clear is not None or clear_launch_ws is not None:
+        raise ValueError(f"{name}: nothing is launched for an empty batch, nothing is cleared")
+    return Mw, source, target, img
+
+
 # ------------------------------------------------- Levenberg-Marquardt registration (libdiffdrr_lm_hip.so)
 def _launch_lm(name, device, *args):
     """:func:`_launch` through the Levenberg-Marquardt library."""
@@ -1736,9 +1840,7 @@ def _query_lm(name, *args):
 def lm_workspace(B, N, device):
     """The (uninitialised) per-workgroup partial sums of :func:`lm_normal_sums` for B poses of N rays:
     (B, ceil(N / 1024), 44) float64."""
-    n = int(_query_lm("ddrr_lm_workspace_bytes", int(B), int(N))) // 8
-    return torch.empty(n, dtype=torch.float64, device=device).view(B, -1, _lib.LM_SUMS) if n else \
-        torch.empty(B, 0, _lib.LM_SUMS, dtype=torch.float64, device=device)
+    return _lm_workspace(_query_lm("ddrr_lm_workspace_bytes", int(B), int(N)), B, _lib.LM_SUMS, device)
 
 
 def lm_state(B, damping, device):
@@ -1757,23 +1859,21 @@ def lm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient34, 
     jac (B, N, 6) float32 | None)."""
     _require_gpu(rot)
     B, N = rot.shape[0], P.shape[0]
-    if fixed.dim() != 2 or fixed.shape[0] not in (1, B) or fixed.shape[1] != N or fixed.dtype != torch.float32:
-        raise ValueError(f"lm_normal_sums: a float32 fixed image of shape (1 | {B}, {N}) expected, got "
-                         f"{tuple(fixed.shape)} {fixed.dtype}")
+    _check_lm_image("lm_normal_sums", fixed, "fixed image", (1, B), N)
     if B > _lib.LM_MAX_POSES:
         raise ValueError(f"lm_normal_sums: at most {_lib.LM_MAX_POSES} poses, got {B}")
-    shared = fixed.shape[0] == 1 and B != 1
     fixed, source = fixed.contiguous(), source.contiguous()
     held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
     dev = rot.device
     if ws is None:
         ws = lm_workspace(B, N, dev)
-    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != lm_workspace(B, N, "meta").numel():
-        raise ValueError("lm_normal_sums: ws must be what lm_workspace(B, N, device) returns")
+    else:
+        _check_lm_ws("lm_normal_sums", ws, lm_workspace, B, N)
     jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
     if B and N:
-        _launch_lm("ddrr_lm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), 0 if shared else N,
-                   source.data_ptr(), *chain, B, N, float(eps), int(bool(with_img_path)), ws.data_ptr(), _ptr(jac))
+        _launch_lm("ddrr_lm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(),
+                   0 if (fixed.shape[0] == 1 and B != 1) else N, source.data_ptr(), *chain, B, N, float(eps),
+                   int(bool(with_img_path)), ws.data_ptr(), _ptr(jac))
     return ws, jac
 
 
@@ -1784,15 +1884,9 @@ def lm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, dam
     ddrr_lm_step) -> the best NCC per pose (B,) float32."""
     _require_gpu(rot)
     B = rot.shape[0]
-    for t in (rot, xyz):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, 3):
-            raise ValueError("lm_step: contiguous float32 (B, 3) pose parameters")
-    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (B, _lib.LM_STATE_DOUBLES):
-        raise ValueError(f"lm_step: state must be a contiguous float64 (B, {_lib.LM_STATE_DOUBLES}) tensor")
-    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != lm_workspace(B, N, "meta").numel():
-        raise ValueError("lm_step: ws must be what lm_workspace(B, N, device) returns")
-    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
-        raise ValueError("lm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
+    _check_lm_state("lm_step", rot, xyz, state)
+    _check_lm_ws("lm_step", ws, lm_workspace, B, N)
+    _check_lm_hyper("lm_step", ncc_eps, up, down, damping_min, damping_max)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=rot.device)
     if B:
@@ -1815,9 +1909,7 @@ def _query_wlm(name, *args):
 def wlm_workspace(B, N, device):
     """The (uninitialised) per-workgroup partial sums of :func:`wlm_normal_sums` for B poses of N rays:
     (B, ceil(N / 1024), 45) float64."""
-    n = int(_query_wlm("ddrr_wlm_workspace_bytes", int(B), int(N))) // 8
-    return torch.empty(n, dtype=torch.float64, device=device).view(B, -1, _lib.WLM_SUMS) if n else \
-        torch.empty(B, 0, _lib.WLM_SUMS, dtype=torch.float64, device=device)
+    return _lm_workspace(_query_wlm("ddrr_wlm_workspace_bytes", int(B), int(N)), B, _lib.WLM_SUMS, device)
 
 
 def wlm_normal_sums(aux, fixed, weight, *, source, Mw, Ainv, P, rot, xyz, axes, reorient34, eps=1e-8,
@@ -1829,25 +1921,17 @@ def wlm_normal_sums(aux, fixed, weight, *, source, Mw, Ainv, P, rot, xyz, axes, 
     _require_gpu(rot)
     B, N = rot.shape[0], P.shape[0]
     dev = rot.device
-    if fixed.dim() != 2 or fixed.shape[0] not in (1, B) or fixed.shape[1] != N or fixed.dtype != torch.float32:
-        raise ValueError(f"wlm_normal_sums: a float32 fixed image of shape (1 | {B}, {N}) expected, got "
-                         f"{tuple(fixed.shape)} {fixed.dtype}")
-    if not torch.is_tensor(weight) or weight.dim() != 2 or weight.shape[0] not in (1, B) or weight.shape[1] != N \
-            or weight.dtype != torch.float32:
-        raise ValueError(f"wlm_normal_sums: a float32 weight of shape (1 | {B}, {N}) expected, got "
-                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__} "
-                         f"{getattr(weight, 'dtype', '')}")
-    for what, t in (("fixed image", fixed), ("weight", weight)):
-        if t.device != dev:
-            raise ValueError(f"wlm_normal_sums: the {what} must live on the poses' device ({dev}), got {t.device}")
+    _check_lm_image("wlm_normal_sums", fixed, "fixed image", (1, B), N)
+    _check_lm_image("wlm_normal_sums", weight, "weight", (1, B), N)
+    _check_lm_devices("wlm_normal_sums", dev, ("the fixed image", fixed), ("the weight", weight))
     if B > _lib.WLM_MAX_POSES:
         raise ValueError(f"wlm_normal_sums: at most {_lib.WLM_MAX_POSES} poses, got {B}")
     fixed, weight, source = fixed.contiguous(), weight.contiguous(), source.contiguous()
     held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient34)
     if ws is None:
         ws = wlm_workspace(B, N, dev)
-    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != wlm_workspace(B, N, "meta").numel():
-        raise ValueError("wlm_normal_sums: ws must be what wlm_workspace(B, N, device) returns")
+    else:
+        _check_lm_ws("wlm_normal_sums", ws, wlm_workspace, B, N)
     jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
     if B and N:
         _launch_wlm("ddrr_wlm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(),
@@ -1864,15 +1948,9 @@ def wlm_step(ws, state, rot, xyz, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0, da
     -> the best weighted NCC per pose (B,) float32."""
     _require_gpu(rot)
     B = rot.shape[0]
-    for t in (rot, xyz):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, 3):
-            raise ValueError("wlm_step: contiguous float32 (B, 3) pose parameters")
-    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (B, _lib.WLM_STATE_DOUBLES):
-        raise ValueError(f"wlm_step: state must be a contiguous float64 (B, {_lib.WLM_STATE_DOUBLES}) tensor")
-    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != wlm_workspace(B, N, "meta").numel():
-        raise ValueError("wlm_step: ws must be what wlm_workspace(B, N, device) returns")
-    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
-        raise ValueError("wlm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
+    _check_lm_state("wlm_step", rot, xyz, state)
+    _check_lm_ws("wlm_step", ws, wlm_workspace, B, N)
+    _check_lm_hyper("wlm_step", ncc_eps, up, down, damping_min, damping_max)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=rot.device)
     if B:
@@ -1892,28 +1970,11 @@ def _query_mvlm(name, *args):
     return _lib.get_mvlm_lib().query(name, *args)
 
 
-def _mvlm_views(name, rot, xyz, reorient_v):
-    """(S, V) of (S, 3) parameters and (V, 3, 4) float32 reorients; refuses what the entries would misread."""
-    S = rot.shape[0]
-    for t in (rot, xyz):
-        if t.dtype != torch.float32 or t.shape != (S, 3):
-            raise ValueError(f"{name}: float32 (S, 3) pose parameters expected, got {tuple(t.shape)} {t.dtype}")
-    if reorient_v.dim() != 3 or reorient_v.shape[0] < 1 or tuple(reorient_v.shape[1:]) != (3, 4) \
-            or reorient_v.dtype != torch.float32:
-        raise ValueError(f"{name}: reorient_v must be a float32 (V, 3, 4) tensor with V >= 1, got "
-                         f"{tuple(reorient_v.shape)} {reorient_v.dtype}")
-    V = reorient_v.shape[0]
-    if S * V > _lib.MVLM_MAX_POSES:
-        raise ValueError(f"{name}: at most {_lib.MVLM_MAX_POSES} poses (S * V), got {S} * {V}")
-    return S, V
-
-
 def mvlm_workspace(S, V, N, device):
     """The (uninitialised) per-workgroup partial sums of :func:`mvlm_normal_sums` for S starts seen from V views
     with N rays: (S * V, ceil(N / 1024), 44) float64."""
-    n = int(_query_mvlm("ddrr_mvlm_workspace_bytes", int(S), int(V), int(N))) // 8
-    return torch.empty(n, dtype=torch.float64, device=device).view(S * V, -1, _lib.MVLM_SUMS) if n else \
-        torch.empty(S * V, 0, _lib.MVLM_SUMS, dtype=torch.float64, device=device)
+    return _lm_workspace(_query_mvlm("ddrr_mvlm_workspace_bytes", int(S), int(V), int(N)), S * V, _lib.MVLM_SUMS,
+                         device)
 
 
 def mvlm_raygen(rot, xyz, axes, reorient_v, Ainv, P, *, clear=None, clear_launch_ws=None):
@@ -1922,21 +1983,9 @@ def mvlm_raygen(rot, xyz, axes, reorient_v, Ainv, P, *, clear=None, clear_launch
     -> (Mw (S V, 3, 4), source_v (S V, 1, 3), target_v (S V, N, 3), img (S V, N)).  ``clear`` and ``clear_launch_ws``
     as there."""
     _require_gpu(rot)
-    S, V = _mvlm_views("mvlm_raygen", rot, xyz, reorient_v)
-    N, B = P.shape[0], S * V
-    rot, xyz, reorient_v, Ainv, P = (t.contiguous() for t in (rot, xyz, reorient_v, Ainv, P))
-    dev = rot.device
-    Mw = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
-    source = torch.empty(B, 1, 3, dtype=torch.float32, device=dev)
-    target = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-    img = torch.empty(B, N, dtype=torch.float32, device=dev)
-    if not _empty(B, N):
-        _launch_mvlm("ddrr_mvlm_raygen", dev, rot.data_ptr(), xyz.data_ptr(), *axes, reorient_v.data_ptr(),
-                     Ainv.data_ptr(), P.data_ptr(), S, V, N, Mw.data_ptr(), source.data_ptr(), target.data_ptr(),
-                     img.data_ptr(), _ptr(clear), 0 if clear is None else clear.numel(), _ptr(clear_launch_ws))
-    elif clear is not None or clear_launch_ws is not None:
-        raise ValueError("mvlm_raygen: nothing is launched for an empty batch, nothing is cleared")
-    return Mw, source, target, img
+    S, V = _lm_views("mvlm_raygen", rot, xyz, reorient_v)
+    return _lm_raygen("mvlm_raygen", _launch_mvlm, rot, xyz, axes, reorient_v, Ainv, P, (), S, V, P.shape[0], clear,
+                      clear_launch_ws)
 
 
 def mvlm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient_v, *, eps=1e-8, with_img_path=True,
@@ -1946,16 +1995,11 @@ def mvlm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient_v
     ``xyz`` (S, 3); ``reorient_v`` (V, 3, 4); the rest as :func:`mvlm_raygen` made them)
     -> (ws (S V, G, 44) float64 per-workgroup partials, jac (S V, N, 6) float32 | None)."""
     _require_gpu(rot)
-    S, V = _mvlm_views("mvlm_normal_sums", rot, xyz, reorient_v)
+    S, V = _lm_views("mvlm_normal_sums", rot, xyz, reorient_v)
     N, B = P.shape[0], S * V
     dev = rot.device
-    if not torch.is_tensor(fixed) or fixed.shape != (V, N) or fixed.dtype != torch.float32:
-        raise ValueError(f"mvlm_normal_sums: a float32 fixed image per view, ({V}, {N}), expected, got "
-                         f"{tuple(fixed.shape) if torch.is_tensor(fixed) else type(fixed).__name__} "
-                         f"{getattr(fixed, 'dtype', '')}")
-    if fixed.device != dev:
-        raise ValueError(f"mvlm_normal_sums: the fixed images must live on the poses' device ({dev}), got "
-                         f"{fixed.device}")
+    _check_lm_image("mvlm_normal_sums", fixed, "fixed image", (V,), N)
+    _check_lm_devices("mvlm_normal_sums", dev, ("the fixed images", fixed))
     if Mw.shape[0] != B or source.shape[0] != B:
         raise ValueError(f"mvlm_normal_sums: Mw and source of {B} poses (S * V) expected, got {Mw.shape[0]} and "
                          f"{source.shape[0]}")
@@ -1963,8 +2007,8 @@ def mvlm_normal_sums(aux, fixed, source, Mw, Ainv, P, rot, xyz, axes, reorient_v
     held, chain = _pose_chain(Mw, Ainv, P, rot, xyz, axes, reorient_v)
     if ws is None:
         ws = mvlm_workspace(S, V, N, dev)
-    elif ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != mvlm_workspace(S, V, N, "meta").numel():
-        raise ValueError("mvlm_normal_sums: ws must be what mvlm_workspace(S, V, N, device) returns")
+    else:
+        _check_lm_ws("mvlm_normal_sums", ws, mvlm_workspace, S, V, N)
     jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
     if B and N:
         _launch_mvlm("ddrr_mvlm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), source.data_ptr(), *chain, S, V,
@@ -1982,18 +2026,10 @@ def mvlm_step(ws, state, rot, xyz, V, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.0
     S, V = rot.shape[0], int(V)
     if V < 1 or S * V > _lib.MVLM_MAX_POSES:
         raise ValueError(f"mvlm_step: V >= 1 and at most {_lib.MVLM_MAX_POSES} poses (S * V) expected, got {S} * {V}")
-    for t in (rot, xyz):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (S, 3):
-            raise ValueError("mvlm_step: contiguous float32 (S, 3) pose parameters")
-    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (S, _lib.MVLM_STATE_DOUBLES):
-        raise ValueError(f"mvlm_step: state must be a contiguous float64 (S, {_lib.MVLM_STATE_DOUBLES}) tensor")
-    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() != mvlm_workspace(S, V, N, "meta").numel():
-        raise ValueError("mvlm_step: ws must be what mvlm_workspace(S, V, N, device) returns")
-    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
-        raise ValueError("mvlm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 expected")
-    if ncc_views is not None and (ncc_views.dtype != torch.float32 or not ncc_views.is_contiguous()
-                                  or ncc_views.shape != (S, V) or ncc_views.device != rot.device):
-        raise ValueError(f"mvlm_step: ncc_views must be a contiguous float32 ({S}, {V}) tensor on the poses' device")
+    _check_lm_state("mvlm_step", rot, xyz, state, "S")
+    _check_lm_ws("mvlm_step", ws, mvlm_workspace, S, V, N)
+    _check_lm_hyper("mvlm_step", ncc_eps, up, down, damping_min, damping_max)
+    _check_lm_views_out("mvlm_step", S, V, rot.device, ncc_views=(ncc_views, torch.float32))
     if out is None:
         out = torch.empty(S, dtype=torch.float32, device=rot.device)
     if S:
@@ -2013,44 +2049,11 @@ def _query_wmvlm(name, *args):
     return _lib.get_wmvlm_lib().query(name, *args)
 
 
-def _wmvlm_views(name, rot, xyz, reorient_v, P):
-    """(S, V, N, P_stride) of (S, 3) parameters, (V, 3, 4) float32 reorients and the detector points, (N, 3) shared
-    by the views (stride 0) or (V, N, 3) (stride 3 N); refuses what the entries would misread."""
-    S = rot.shape[0]
-    dev = rot.device
-    for t in (rot, xyz):
-        if t.dtype != torch.float32 or t.shape != (S, 3):
-            raise ValueError(f"{name}: float32 (S, 3) pose parameters expected, got {tuple(t.shape)} {t.dtype}")
-    if reorient_v.dim() != 3 or reorient_v.shape[0] < 1 or tuple(reorient_v.shape[1:]) != (3, 4) \
-            or reorient_v.dtype != torch.float32:
-        raise ValueError(f"{name}: reorient_v must be a float32 (V, 3, 4) tensor with V >= 1, got "
-                         f"{tuple(reorient_v.shape)} {reorient_v.dtype}")
-    V = reorient_v.shape[0]
-    if S * V > _lib.WMVLM_MAX_POSES:
-        raise ValueError(f"{name}: at most {_lib.WMVLM_MAX_POSES} poses (S * V), got {S} * {V}")
-    if not torch.is_tensor(P) or P.dtype != torch.float32 or P.dim() not in (2, 3) or P.shape[-1] != 3 \
-            or (P.dim() == 3 and P.shape[0] != V):
-        raise ValueError(f"{name}: the detector points must be float32 (N, 3), shared by the views, or ({V}, N, 3), "
-                         f"got {tuple(P.shape) if torch.is_tensor(P) else type(P).__name__} {getattr(P, 'dtype', '')}")
-    for what, t in (("xyz", xyz), ("reorient_v", reorient_v), ("detector points", P)):
-        if t.device != dev:
-            raise ValueError(f"{name}: {what} must live on the poses' device ({dev}), got {t.device}")
-    N = P.shape[-2]
-    return S, V, N, (3 * N if P.dim() == 3 else 0)
-
-
 def wmvlm_workspace(S, V, N, device):
     """The (uninitialised) per-workgroup partial sums of :func:`wmvlm_normal_sums` for S starts seen from V views
     with N rays: (S * V, ceil(N / 1024), 45) float64."""
-    n = int(_query_wmvlm("ddrr_wmvlm_workspace_bytes", int(S), int(V), int(N))) // 8
-    return torch.empty(n, dtype=torch.float64, device=device).view(S * V, -1, _lib.WMVLM_SUMS) if n else \
-        torch.empty(S * V, 0, _lib.WMVLM_SUMS, dtype=torch.float64, device=device)
-
-
-def _wmvlm_ws(name, ws, S, V, N):
-    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.dim() != 3 or ws.shape[-1] != _lib.WMVLM_SUMS \
-            or ws.numel() != wmvlm_workspace(S, V, N, "meta").numel():
-        raise ValueError(f"{name}: ws must be what wmvlm_workspace(S, V, N, device) returns")
+    return _lm_workspace(_query_wmvlm("ddrr_wmvlm_workspace_bytes", int(S), int(V), int(N)), S * V, _lib.WMVLM_SUMS,
+                         device)
 
 
 def wmvlm_raygen(rot, xyz, axes, reorient_v, Ainv, P, *, clear=None, clear_launch_ws=None):
@@ -2060,22 +2063,9 @@ def wmvlm_raygen(rot, xyz, axes, reorient_v, Ainv, P, *, clear=None, clear_launc
     -> (Mw (S V, 3, 4), source_v (S V, 1, 3), target_v (S V, N, 3), img (S V, N)).  ``clear`` and ``clear_launch_ws``
     as there."""
     _require_gpu(rot)
-    S, V, N, P_stride = _wmvlm_views("wmvlm_raygen", rot, xyz, reorient_v, P)
-    B = S * V
-    rot, xyz, reorient_v, Ainv, P = (t.contiguous() for t in (rot, xyz, reorient_v, Ainv, P))
-    dev = rot.device
-    Mw = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
-    source = torch.empty(B, 1, 3, dtype=torch.float32, device=dev)
-    target = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-    img = torch.empty(B, N, dtype=torch.float32, device=dev)
-    if not _empty(B, N):
-        _launch_wmvlm("ddrr_wmvlm_raygen", dev, rot.data_ptr(), xyz.data_ptr(), *axes, reorient_v.data_ptr(),
-                      Ainv.data_ptr(), P.data_ptr(), P_stride, S, V, N, Mw.data_ptr(), source.data_ptr(),
-                      target.data_ptr(), img.data_ptr(), _ptr(clear), 0 if clear is None else clear.numel(),
-                      _ptr(clear_launch_ws))
-    elif clear is not None or clear_launch_ws is not None:
-        raise ValueError("wmvlm_raygen: nothing is launched for an empty batch, nothing is cleared")
-    return Mw, source, target, img
+    S, V, N, P_stride = _lm_views("wmvlm_raygen", rot, xyz, reorient_v, P, max_poses=_lib.WMVLM_MAX_POSES)
+    return _lm_raygen("wmvlm_raygen", _launch_wmvlm, rot, xyz, axes, reorient_v, Ainv, P, (P_stride,), S, V, N, clear,
+                      clear_launch_ws)
 
 
 def wmvlm_normal_sums(aux, fixed, weight, source, Mw, Ainv, P, rot, xyz, axes, reorient_v, *, eps=1e-8,
@@ -2087,21 +2077,13 @@ def wmvlm_normal_sums(aux, fixed, weight, source, Mw, Ainv, P, rot, xyz, axes, r
     :func:`wmvlm_raygen` made them)
     -> (ws (S V, G, 45) float64 per-workgroup partials, jac (S V, N, 6) float32 | None)."""
     _require_gpu(rot)
-    S, V, N, P_stride = _wmvlm_views("wmvlm_normal_sums", rot, xyz, reorient_v, P)
+    S, V, N, P_stride = _lm_views("wmvlm_normal_sums", rot, xyz, reorient_v, P,
+                                      max_poses=_lib.WMVLM_MAX_POSES)
     B = S * V
     dev = rot.device
-    if not torch.is_tensor(fixed) or fixed.shape != (V, N) or fixed.dtype != torch.float32:
-        raise ValueError(f"wmvlm_normal_sums: a float32 fixed image per view, ({V}, {N}), expected, got "
-                         f"{tuple(fixed.shape) if torch.is_tensor(fixed) else type(fixed).__name__} "
-                         f"{getattr(fixed, 'dtype', '')}")
-    if not torch.is_tensor(weight) or weight.dim() != 2 or weight.shape[0] not in (1, V) or weight.shape[1] != N \
-            or weight.dtype != torch.float32:
-        raise ValueError(f"wmvlm_normal_sums: a float32 weight of shape (1 | {V}, {N}) expected, got "
-                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__} "
-                         f"{getattr(weight, 'dtype', '')}")
-    for what, t in (("fixed images", fixed), ("weight", weight)):
-        if t.device != dev:
-            raise ValueError(f"wmvlm_normal_sums: the {what} must live on the poses' device ({dev}), got {t.device}")
+    _check_lm_image("wmvlm_normal_sums", fixed, "fixed image", (V,), N)
+    _check_lm_image("wmvlm_normal_sums", weight, "weight", (1, V), N)
+    _check_lm_devices("wmvlm_normal_sums", dev, ("the fixed images", fixed), ("the weight", weight))
     if Mw.shape[0] != B or source.shape[0] != B:
         raise ValueError(f"wmvlm_normal_sums: Mw and source of {B} poses (S * V) expected, got {Mw.shape[0]} and "
                          f"{source.shape[0]}")
@@ -2110,7 +2092,7 @@ def wmvlm_normal_sums(aux, fixed, weight, source, Mw, Ainv, P, rot, xyz, axes, r
     if ws is None:
         ws = wmvlm_workspace(S, V, N, dev)
     else:
-        _wmvlm_ws("wmvlm_normal_sums", ws, S, V, N)
+        _check_lm_ws("wmvlm_normal_sums", ws, wmvlm_workspace, S, V, N, sums=_lib.WMVLM_SUMS)
     jac = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if want_jacobian else None
     if B and N:
         _launch_wmvlm("ddrr_wmvlm_normal_sums", dev, aux.data_ptr(), fixed.data_ptr(), weight.data_ptr(),
@@ -2133,23 +2115,13 @@ def wmvlm_step(ws, state, rot, xyz, V, N, *, ncc_eps=1e-5, up=4.0, down=1.0 / 3.
     if V < 1 or S * V > _lib.WMVLM_MAX_POSES:
         raise ValueError(f"wmvlm_step: V >= 1 and at most {_lib.WMVLM_MAX_POSES} poses (S * V) expected, got "
                          f"{S} * {V}")
-    for t in (rot, xyz):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (S, 3):
-            raise ValueError("wmvlm_step: contiguous float32 (S, 3) pose parameters")
-    if state.dtype != torch.float64 or not state.is_contiguous() or state.shape != (S, _lib.WMVLM_STATE_DOUBLES):
-        raise ValueError(f"wmvlm_step: state must be a contiguous float64 (S, {_lib.WMVLM_STATE_DOUBLES}) tensor")
-    _wmvlm_ws("wmvlm_step", ws, S, V, N)
-    for what, t in (("xyz", xyz), ("state", state), ("ws", ws)):
-        if t.device != rot.device:
-            raise ValueError(f"wmvlm_step: {what} must live on the poses' device ({rot.device}), got {t.device}")
-    if not (up > 1.0 and 0.0 < down < 1.0 and 0.0 < damping_min <= damping_max < float("inf") and ncc_eps >= 0.0):
-        raise ValueError("wmvlm_step: up > 1, 0 < down < 1, 0 < damping_min <= damping_max < inf, ncc_eps >= 0 "
-                         "expected")
-    for what, t, dtype in (("ncc_views", ncc_views, torch.float32), ("sw_views", sw_views, torch.float64)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.shape != (S, V)
-                              or t.device != rot.device):
-            raise ValueError(f"wmvlm_step: {what} must be a contiguous {str(dtype)[6:]} ({S}, {V}) tensor on the "
-                             "poses' device")
+    _check_lm_state("wmvlm_step", rot, xyz, state, "S")
+    _check_lm_ws("wmvlm_step", ws, wmvlm_workspace, S, V, N, sums=_lib.WMVLM_SUMS)
+    # (the other three steps do not look at the devices)
+    _check_lm_devices("wmvlm_step", rot.device, ("xyz", xyz), ("state", state), ("ws", ws))
+    _check_lm_hyper("wmvlm_step", ncc_eps, up, down, damping_min, damping_max)
+    _check_lm_views_out("wmvlm_step", S, V, rot.device, ncc_views=(ncc_views, torch.float32),
+                        sw_views=(sw_views, torch.float64))
     if out is None:
         out = torch.empty(S, dtype=torch.float32, device=rot.device)
     if S:

@@ -19,6 +19,7 @@ from diffdrr_amd.data import synthetic_subject
 from diffdrr_amd.registration import normal_equations_reference
 
 EMU_SRC = os.path.join(ROOT, "tests", "emu", "lm_emu.cpp")
+EMU_LOOPS = os.path.join(ROOT, "tests", "emu", "lm_emu_loops.h")  # the loops of the four host builds
 EMU_SO = os.path.join(ROOT, "tests", "emu", "_build", "liblm_emu.so")
 FLOOR = 1e-6
 
@@ -30,6 +31,8 @@ SUM_CASES = {
     "780_rays_zyx_stop": ((30, 26), 3.0, 3, "ZYX", True),
     "4087_rays_four_workgroups": ((67, 61), 1.3, 2, "ZXY", False),
     "6_rays": ((2, 3), 20.0, 1, "ZXY", False),
+    # two workgroups, the second of a single ray: fewer rays than slices, and three of a thread's four rays clamped
+    "1025_rays": ((25, 41), 2.4, 2, "ZYX", False),
 }
 
 
@@ -37,7 +40,7 @@ SUM_CASES = {
 def emu_library():
     """The host build of the two entries (tests/emu/lm_emu.cpp), bound through the product's own binding."""
     csrc = os.path.join(ROOT, "diffdrr_amd", "csrc")
-    deps = [EMU_SRC, os.path.join(ROOT, "include", "diffdrr_lm_hip.h")] + [
+    deps = [EMU_SRC, EMU_LOOPS, os.path.join(ROOT, "include", "diffdrr_lm_hip.h")] + [
         os.path.join(csrc, f) for f in ("lm_core.h", "siddon_core.h", "raygen_core.h", "record_layout.h",
                                         "ddrr_common.h")]
     if not (os.path.exists(EMU_SO) and all(os.path.getmtime(d) <= os.path.getmtime(EMU_SO) for d in deps)):

@@ -19,7 +19,7 @@ def test_bit_for_bit_properties(gpu, name):
     wlm_cases.check_bit_for_bit_properties(name, gpu, ops)
 
 
-@pytest.mark.parametrize("name", ("780_rays_zyx_stop", "4087_rays_four_workgroups"))
+@pytest.mark.parametrize("name", ("780_rays_zyx_stop", "4087_rays_four_workgroups", "1025_rays"))
 def test_device_sums_equal_the_host_order_bit_for_bit_given_the_same_rows(gpu, name):
     wlm_cases.check_device_sums_from_the_devices_own_rows(name, gpu, ops)
 
@@ -29,7 +29,7 @@ def test_masked_pixels_are_not_read(gpu, name):
     wlm_cases.check_masked_pixels_are_not_read(name, gpu, ops)
 
 
-@pytest.mark.parametrize("name", ("780_rays_zxy", "4087_rays_four_workgroups"))
+@pytest.mark.parametrize("name", ("780_rays_zxy", "4087_rays_four_workgroups", "1025_rays"))
 def test_power_of_four_scaling_of_the_weight(gpu, name):
     wlm_cases.check_power_of_four_scaling(name, gpu, ops)
 

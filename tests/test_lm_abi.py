@@ -80,6 +80,16 @@ def test_build_calls_the_library_build():
     assert entry.LM_LIB == _lib.LM_LIB_PATH
 
 
+def test_the_kernel_bodies_of_the_four_libraries_are_written_once():
+    """The record loads, the pose prologue of the sums and the pose of the ray generation are called in exactly one
+    of the four libraries' sources and lm_kernels.h: the bodies are shared, not copied."""
+    csrc = os.path.join(ROOT, "diffdrr_amd", "csrc")
+    files = ("lm.hip", "wlm.hip", "mvlm.hip", "wmvlm.hip", "lm_kernels.h")
+    text = {f: open(os.path.join(csrc, f)).read() for f in files}
+    for call in ("rec_blocked_load(", "pose_euler_adjoint_setup(", "pose_euler_forward("):
+        assert [f for f in files if call in text[f]] == ["lm_kernels.h"], call
+
+
 def test_library_contains_gfx950_code_object(lm):
     blob = open(_lib.LM_LIB_PATH, "rb").read()
     assert b"gfx950" in blob

@@ -54,7 +54,7 @@ def test_masked_pixels_are_not_read(wlm_ops, name):
     wlm_cases.check_masked_pixels_are_not_read(name, CPU, wlm_ops)
 
 
-@pytest.mark.parametrize("name", ("780_rays_zxy", "4087_rays_four_workgroups"))
+@pytest.mark.parametrize("name", ("780_rays_zxy", "4087_rays_four_workgroups", "1025_rays"))
 def test_power_of_four_scaling_of_the_weight(wlm_ops, name):
     wlm_cases.check_power_of_four_scaling(name, CPU, wlm_ops)
 

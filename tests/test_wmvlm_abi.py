@@ -77,16 +77,22 @@ def test_the_other_headers_and_their_versions_are_untouched():
 
 
 def test_the_parent_sources_are_not_part_of_this_library():
-    """The library includes the cores of its parents and defines none of their arithmetic again: its sources name
-    the functions they call and hold no second definition of them."""
+    """The library includes the cores of its parents and defines none of their arithmetic again: its sources -- with
+    lm_kernels.h, where the kernels' bodies are written once for the four libraries -- name the functions they call
+    and hold no second definition of them.  The weighted sums are called through wlm_core.h's WeightedSums, which
+    the normal-sums kernel is instantiated on."""
     csrc = os.path.join(ROOT, "diffdrr_amd", "csrc")
     core = open(os.path.join(csrc, "wmvlm_core.h")).read()
     hip = open(os.path.join(csrc, "wmvlm.hip")).read()
-    assert '#include "wlm_core.h"' in core and '#include "wmvlm_core.h"' in hip
-    assert '#include "lm_core.h"' in open(os.path.join(csrc, "wlm_core.h")).read()
+    kernels = open(os.path.join(csrc, "lm_kernels.h")).read()
+    wlm_core = open(os.path.join(csrc, "wlm_core.h")).read()
+    assert '#include "wlm_core.h"' in core and '#include "wmvlm_core.h"' in hip and '#include "lm_kernels.h"' in hip
+    assert '#include "lm_core.h"' in wlm_core and '#include "lm_core.h"' in kernels
+    assert "normal_sums_body<WeightedSums>(" in hip and "Sums::slice(" in kernels
+    assert re.search(r"struct WeightedSums \{[^}]*\bwslice_sum\(", wlm_core)
     for fn in ("ray_jacobian", "wslice_sum", "normal_equations", "judge_and_solve"):
-        assert fn + "(" in core + hip, fn
-        assert not re.search(r"DDRR_HD\s+[\w:&\s]+\b" + fn + r"\s*\(", core + hip), fn
+        assert fn + "(" in core + hip + kernels or fn == "wslice_sum", fn
+        assert not re.search(r"DDRR_HD\s+[\w:&\s]+\b" + fn + r"\s*\(", core + hip + kernels), fn
 
 
 def test_library_builds_loads_and_exports_exactly_the_header(wmvlm):

@@ -35,7 +35,8 @@ GROUP = _lib.WLM_GROUP_RAYS
 def emu_library():
     """The host build of the two entries (tests/emu/wlm_emu.cpp), bound through the product's own binding."""
     csrc = os.path.join(ROOT, "diffdrr_amd", "csrc")
-    deps = [EMU_SRC] + [os.path.join(ROOT, "include", f) for f in ("diffdrr_wlm_hip.h", "diffdrr_lm_hip.h")]
+    deps = [EMU_SRC, lm_cases.EMU_LOOPS]
+    deps += [os.path.join(ROOT, "include", f) for f in ("diffdrr_wlm_hip.h", "diffdrr_lm_hip.h")]
     deps += [os.path.join(csrc, f) for f in ("wlm_core.h", "lm_core.h", "siddon_core.h", "raygen_core.h",
                                              "record_layout.h", "ddrr_common.h")]
     if not (os.path.exists(EMU_SO) and all(os.path.getmtime(d) <= os.path.getmtime(EMU_SO) for d in deps)):

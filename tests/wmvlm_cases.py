@@ -40,16 +40,17 @@ EMU_SRC = os.path.join(ROOT, "tests", "emu", "wmvlm_emu.cpp")
 EMU_SO = os.path.join(ROOT, "tests", "emu", "_build", "libwmvlm_emu.so")
 GROUP = _lib.WMVLM_GROUP_RAYS
 SMALL = ("6_rays", "780_rays_zxy", "780_rays_zyx_stop")  # the scenes with a float64 route
-NAMES = SMALL + ("4087_rays_four_workgroups",)            # ... and the one for bit-for-bit checks only
+NAMES = SMALL + ("4087_rays_four_workgroups", "1025_rays")  # ... and the ones for bit-for-bit checks only
 
 
 @functools.lru_cache(maxsize=None)
 def emu_library():
     """The host build of the three entries (tests/emu/wmvlm_emu.cpp), bound through the product's own binding."""
     csrc = os.path.join(ROOT, "diffdrr_amd", "csrc")
-    deps = [EMU_SRC] + [os.path.join(ROOT, "include", f) for f in ("diffdrr_wmvlm_hip.h", "diffdrr_wlm_hip.h",
-                                                                   "diffdrr_lm_hip.h")]
-    deps += [os.path.join(csrc, f) for f in ("wmvlm_core.h", "wlm_core.h", "lm_core.h", "siddon_core.h",
+    deps = [EMU_SRC, lm_cases.EMU_LOOPS]
+    deps += [os.path.join(ROOT, "include", f) for f in ("diffdrr_wmvlm_hip.h", "diffdrr_mvlm_hip.h",
+                                                        "diffdrr_wlm_hip.h", "diffdrr_lm_hip.h")]
+    deps += [os.path.join(csrc, f) for f in ("wmvlm_core.h", "mvlm_core.h", "wlm_core.h", "lm_core.h", "siddon_core.h",
                                              "raygen_core.h", "record_layout.h", "ddrr_common.h")]
     if not (os.path.exists(EMU_SO) and all(os.path.getmtime(d) <= os.path.getmtime(EMU_SO) for d in deps)):
         os.makedirs(os.path.dirname(EMU_SO), exist_ok=True)
