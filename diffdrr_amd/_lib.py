@@ -39,6 +39,7 @@ WNCC_ABI_VERSION = 1
 WLM_ABI_VERSION = 1
 MVLM_ABI_VERSION = 1
 WMVLM_ABI_VERSION = 1
+WMI_ABI_VERSION = 1
 
 _P, _I, _F, _L, _D = c_void_p, c_int, c_float, c_long, c_double
 _ARGTYPES = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
@@ -597,3 +598,34 @@ def get_wmvlm_lib() -> DdrrLibrary:
                 "built. Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         _wmvlm_lib = wmvlm_library(WMVLM_LIB_PATH)
     return _wmvlm_lib
+
+
+# ----------------------------------------------------------------- libdiffdrr_wmi_hip.so
+# MutualInformation under per-pixel weights (C ABI: include/diffdrr_wmi_hip.h): a library of its own next to
+# libdiffdrr_mi_hip.so, which stays as it is
+WMI_LIB_PATH = os.path.join(_HERE, "csrc", "libdiffdrr_wmi_hip.so")
+WMI_HEADER = Header.read("diffdrr_wmi_hip.h", "ddrr_wmi", WMI_ABI_VERSION)
+_WMI_SIGNATURES, _WMI_RESTYPES, WMI_EXPORTS = WMI_HEADER.tables()
+WMI_MAX_BINS, = WMI_HEADER.constants("MAX_BINS")
+
+
+def wmi_library(path: str) -> DdrrLibrary:
+    """Load and check a build of include/diffdrr_wmi_hip.h."""
+    return DdrrLibrary(path, WMI_HEADER)
+
+
+_wmi_lib: DdrrLibrary | None = None
+
+
+def get_wmi_lib() -> DdrrLibrary:
+    """The weighted MutualInformation library, loaded on first use.  Raises if it has not been built."""
+    global _wmi_lib
+    if _wmi_lib is None:
+        import torch  # noqa: F401  (must own the HIP runtime before we bind to it)
+
+        if not os.path.exists(WMI_LIB_PATH):
+            raise RuntimeError(
+                f"{WMI_LIB_PATH} is missing: the weighted MutualInformation kernels have not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
+        _wmi_lib = wmi_library(WMI_LIB_PATH)
+    return _wmi_lib

@@ -362,12 +362,76 @@ def mutual_information(x1, x2, bins, sigma, epsilon=1e-10, normalize=True):
     return mi
 
 
+class _WeightedMIFn(torch.autograd.Function):
+    """:class:`_MIFn` under per-pixel weights: ddrr_wmi_forward / ddrr_wmi_backward (include/diffdrr_wmi_hip.h).
+    x1, x2, w (B or 1, H, W) -> (B,); no gradient w.r.t. w."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w, bins, sigma, epsilon, normalize, B):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, state = ops.wmi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state=want)
+        ctx.B = B
+        ctx.save_for_backward(x1, x2, w, bins, sigma, state)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x1, x2, w, bins, sigma, state = ctx.saved_tensors
+        B = ctx.B
+        grads = [None, None]
+        for which, x in ((0, x1), (1, x2)):
+            if ctx.needs_input_grad[which]:
+                gx = ops.wmi_backward(x1, x2, w, bins, sigma, state, g, which, B)
+                grads[which] = gx.sum(0, keepdim=True) if (x.shape[0] == 1 and B != 1) else gx
+        return grads[0], grads[1], None, None, None, None, None, None
+
+
+def weighted_mutual_information(x1, x2, weight, bins, sigma, epsilon=1e-10, normalize=True):
+    """The weighted mutual information of include/diffdrr_wmi_hip.h as a torch composition: x1, x2 (B, 1, H, W),
+    weight ((1 | B), 1, H, W) >= 0 -> (B,).  :func:`mutual_information` with every sum over the pixels weighted,
+    and the mean of the marginals taken with Sw = sum_n w[n]:
+        P1[k] = sum_n w[n] k1[n,k] / Sw,   J[k,l] = sum_n w[n] k1[n,k] k2[n,l].
+    A pixel of weight 0 is selected out (NaN or Inf there is safe, its gradient is exactly 0); a pair with Sw = 0
+    scores 0 with a zero gradient.  With weight = 1 everywhere: :func:`mutual_information`'s value and gradient.
+    Any dtype, any device; differentiable in x1, x2 and the weight.  Materialises (B, H W, K) kernel values."""
+    B = x1.shape[0]
+    w = weight.expand(B, -1, -1, -1).reshape(B, -1, 1)
+    on = w != 0
+    w = torch.where(on, w, torch.zeros_like(w))
+    Sw = w.sum(dim=1)  # (B, 1)
+    some = Sw > 0
+    Sw1 = torch.where(some, Sw, torch.ones_like(Sw))
+
+    def kernel_values(x):
+        x = torch.where(on, x.reshape(B, -1, 1), torch.zeros_like(w))
+        return torch.exp(-0.5 * ((x - bins) / sigma).pow(2))
+
+    k1, k2 = kernel_values(x1), kernel_values(x2)
+    wk1 = torch.where(on, w * k1, torch.zeros_like(k1))
+    p1 = wk1.sum(dim=1) / Sw1
+    p1 = p1 / (p1.sum(dim=1, keepdim=True) + epsilon)
+    p2 = torch.where(on, w * k2, torch.zeros_like(k2)).sum(dim=1) / Sw1
+    p2 = p2 / (p2.sum(dim=1, keepdim=True) + epsilon)
+    joint = torch.matmul(wk1.transpose(1, 2), k2)
+    p12 = joint / (joint.sum(dim=(1, 2)).view(-1, 1, 1) + 1e-10)  # (joint_pdf's own epsilon)
+    h1 = -(p1 * (p1 + epsilon).log2()).sum(dim=1)
+    h2 = -(p2 * (p2 + epsilon).log2()).sum(dim=1)
+    h12 = -(p12 * (p12 + epsilon).log2()).sum(dim=(1, 2))
+    mi = h1 + h2 - h12
+    some = some.reshape(B)
+    if normalize:
+        # (an empty pair has h1 + h2 = 0: the divisor is selected, so there is no 0 / 0 in the graph)
+        mi = 2 * mi / torch.where(some, h1 + h2, torch.ones_like(h1))
+    return torch.where(some, mi, torch.zeros_like(mi))
+
+
 class MutualInformation(torch.nn.Module):
     """(Normalised) mutual information of two batches of single-channel images from Gaussian-kernel
     density estimates of their marginal and joint intensity distributions (reference metrics.py:110-139).
     float32 images on the device take the fused kernels (num_bins <= 256); everything else -- CPU,
     float64, more bins, ``bins`` / ``sigma`` that require grad (the kernels differentiate the images
-    only) -- the torch composition :func:`mutual_information`."""
+    only) -- the torch composition :func:`mutual_information`.  With ``weight=``: the weighted (masked)
+    criterion, see :meth:`forward`."""
 
     def __init__(self, sigma=0.1, num_bins=256, epsilon=1e-10, normalize=True):
         super().__init__()
@@ -376,13 +440,20 @@ class MutualInformation(torch.nn.Module):
         self.epsilon = epsilon
         self.normalize = normalize
 
-    def forward(self, x1, x2):
+    def forward(self, x1, x2, weight=None):
+        """``weight`` ((1 | B), 1, H, W), >= 0 and finite: the weighted (masked) mutual information of
+        include/diffdrr_wmi_hip.h -- pixels with weight 0 are not read (NaN there is safe) and get the gradient
+        0, a pair whose weights are all 0 scores 0.  float32 images, buffers and weight on the device, with a
+        weight that takes no gradient, go through the kernels of that library (num_bins <= 256); everything else
+        through :func:`weighted_mutual_information`."""
         if x1.shape != x2.shape:
             raise ValueError(f"Input images must be the same size: {tuple(x1.shape)} and {tuple(x2.shape)}")
         if x1.dim() != 4 or x1.shape[1] != 1:
             raise ValueError(f"MutualInformation takes (B, 1, H, W) images, got {tuple(x1.shape)}")
         B, _, H, W = x1.shape
         K = self.bins.numel()
+        if weight is not None:
+            return self._weighted(x1, x2, weight)
         if (ops.on_device(x2) and x1.device == x2.device == self.bins.device == self.sigma.device
                 and x1.dtype == x2.dtype == self.bins.dtype == self.sigma.dtype == torch.float32
                 and self.sigma.numel() == 1 and 1 <= K <= _lib.MI_MAX_BINS and H * W > 0
@@ -393,3 +464,21 @@ class MutualInformation(torch.nn.Module):
             # (the batch size is passed: both images may be expanded)
             return _MIFn.apply(a, b, self.bins, self.sigma, float(self.epsilon), bool(self.normalize), B)
         return mutual_information(x1, x2, self.bins, self.sigma, self.epsilon, self.normalize)
+
+    def _weighted(self, x1, x2, weight):
+        B, _, H, W = x2.shape
+        K = self.bins.numel()
+        if weight.dim() != 4 or weight.shape[0] not in (1, B) or tuple(weight.shape[1:]) != (1, H, W):
+            raise ValueError(f"weight has shape {tuple(weight.shape)}: (1 | {B}, 1, {H}, {W}) expected")
+        if (ops.on_device(x2) and x1.device == x2.device == weight.device == self.bins.device == self.sigma.device
+                and x1.dtype == x2.dtype == weight.dtype == self.bins.dtype == self.sigma.dtype == torch.float32
+                and self.sigma.numel() == 1 and 1 <= K <= _lib.WMI_MAX_BINS and H * W > 0
+                and not (torch.is_grad_enabled() and (self.bins.requires_grad or self.sigma.requires_grad
+                                                      or weight.requires_grad))):
+            a = x1[:1, 0] if (B > 1 and x1.stride(0) == 0) else x1[:, 0]
+            b = x2[:1, 0] if (B > 1 and x2.stride(0) == 0) else x2[:, 0]
+            # (one weight for the batch, given so or `expand`ed, is read in place)
+            w = weight[:1, 0] if (weight.shape[0] == 1 or (B > 1 and weight.stride(0) == 0)) else weight[:, 0]
+            return _WeightedMIFn.apply(a, b, w.detach(), self.bins, self.sigma, float(self.epsilon),
+                                       bool(self.normalize), B)
+        return weighted_mutual_information(x1, x2, weight, self.bins, self.sigma, self.epsilon, self.normalize)

@@ -1570,6 +1570,74 @@ def mi_backward(x1, x2, bins, sigma, state, g_out, which, B):
     return grad
 
 
+# ------------------------------------------------------------------ weighted MutualInformation (libdiffdrr_wmi_hip.so)
+def _launch_wmi(name, device, *args):
+    """:func:`_launch` through the weighted MutualInformation library."""
+    _launch_on(_lib.get_wmi_lib(), name, device, args)
+
+
+def _query_wmi(name, *args):
+    return _lib.get_wmi_lib().query(name, *args)
+
+
+def _wmi_weight(name, w, B, H, W):
+    """(B or 1, H, W) float32 -> (tensor, stride in floats): ONE weight shared by the batch (given so, or
+    `expand`ed) is read in place with stride 0."""
+    if w.dim() != 3 or tuple(w.shape[1:]) != (H, W) or w.shape[0] not in (1, B) or w.dtype != torch.float32:
+        raise ValueError(f"{name}: the weight has shape {tuple(w.shape)} {w.dtype}: float32 ({B}, {H}, {W}), or "
+                         f"(1, {H}, {W}) for one weight shared by the batch, expected")
+    return _mi_image(w, B, H * W)
+
+
+def wmi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state=True, want_weight_sum=False):
+    """:func:`mi_forward` under per-pixel weights w (B or 1, H, W) float32, >= 0 and finite (not looked for;
+    include/diffdrr_wmi_hip.h): pixels with w == 0 are not read, a pair whose weights are all 0 scores 0.
+    -> (mi (B), state (B, S) | None: what :func:`wmi_backward` needs[, the pairs' sums of weights (B) float64,
+    with ``want_weight_sum``])."""
+    _require_gpu(x2)
+    for x in (x1, x2):
+        if x.shape[0] not in (1, B):
+            raise ValueError(f"image batch {x.shape[0]} is neither 1 nor B = {B}")
+    H, W = x2.shape[-2:]
+    K = bins.numel()
+    wt, sw = _wmi_weight("wmi_forward", w, B, H, W)
+    a, s1 = _mi_image(x1, B, H * W)
+    b, s2 = _mi_image(x2, B, H * W)
+    bins, sigma = bins.contiguous(), sigma.contiguous()
+    dev = x2.device
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    state = None
+    if want_state:
+        state = torch.empty(B, int(_query_wmi("ddrr_wmi_state_floats", K)), dtype=torch.float32, device=dev)
+    weight_sum = torch.empty(B, dtype=torch.float64, device=dev) if want_weight_sum else None
+    if B:
+        n = int(_query_wmi("ddrr_wmi_workspace_bytes", B, H, W, K))
+        if n < 0:
+            raise ValueError(_lib.get_wmi_lib()._last_error().decode(errors="replace"))
+        ws = torch.empty((n + 15) // 16, 4, dtype=torch.float32, device=dev)  # (16-byte aligned)
+        _launch_wmi("ddrr_wmi_forward", dev, a.data_ptr(), s1, b.data_ptr(), s2, wt.data_ptr(), sw, B, H, W,
+                    bins.data_ptr(), K, sigma.data_ptr(), float(epsilon), int(bool(normalize)), ws.data_ptr(),
+                    ws.numel() * 4, out.data_ptr(), _ptr(state), _ptr(weight_sum))
+    return (out, state, weight_sum) if want_weight_sum else (out, state)
+
+
+def wmi_backward(x1, x2, w, bins, sigma, state, g_out, which, B):
+    """g_out[b] * d mi[b] / d x2[b] (which = 1) or / d x1[b] (which = 0), (B, H, W), of :func:`wmi_forward`
+    with the same arguments; exactly 0 where w == 0.  A shared differentiated image gets its per-pose gradients
+    (B, H, W)."""
+    H, W = x2.shape[-2:]
+    wt, sw = _wmi_weight("wmi_backward", w, B, H, W)
+    a, s1 = _mi_image(x1, B, H * W)
+    b, s2 = _mi_image(x2, B, H * W)
+    g_out, g_stride = _batch_grad(g_out, B)
+    grad = torch.empty(B, H, W, dtype=torch.float32, device=x2.device)
+    if B:
+        _launch_wmi("ddrr_wmi_backward", x2.device, a.data_ptr(), s1, b.data_ptr(), s2, wt.data_ptr(), sw, B, H, W,
+                    bins.data_ptr(), bins.numel(), sigma.data_ptr(), state.data_ptr(), int(which), g_out.data_ptr(),
+                    g_stride, grad.data_ptr())
+    return grad
+
+
 # ------------------------------------------------------------------ reconstruction (libdiffdrr_recon_hip.so)
 _TV_MODES = {"isotropic": _lib.RECON_TV_ISOTROPIC, "anisotropic": _lib.RECON_TV_ANISOTROPIC}
 

@@ -141,7 +141,8 @@ class GraphedIteration:
 
     ``weight`` ((1 | B), 1, H, W), >= 0: the criterion's per-pixel weight (a mask of the collimator, of dead
     pixels, of instruments the CT does not hold), read in place like ``target``.  The fused route passes it to
-    ``DRR.ncc``, the unfused one calls ``criterion(target, reg(), weight=weight)``."""
+    ``DRR.ncc``, the unfused one calls ``criterion(target, reg(), weight=weight)`` -- ``MutualInformation``
+    included, which then runs its weighted kernels (include/diffdrr_wmi_hip.h) inside the captured graph."""
 
     def __init__(self, reg: Registration, criterion, optimizer, target: torch.Tensor,
                  warmup: int = 3, static_volume: bool = True, fused_similarity: bool = True,
