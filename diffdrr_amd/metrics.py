@@ -314,6 +314,18 @@ class MultiscaleNormalizedCrossCorrelation2d(torch.nn.Module):
         return total
 
 
+def _mi_image_grads(ctx, g, backward):
+    """The backward of :class:`_MIFn` and :class:`_WeightedMIFn`: one launch of `backward` per image that wants a
+    gradient; an image shared by the batch gets the sum over the poses."""
+    *inputs, state = ctx.saved_tensors  # x1, x2, [w,] bins, sigma
+    grads = [None, None]
+    for which in (0, 1):
+        if ctx.needs_input_grad[which]:
+            gx = backward(*inputs, state, g, which, ctx.B)
+            grads[which] = gx.sum(0, keepdim=True) if (inputs[which].shape[0] == 1 and ctx.B != 1) else gx
+    return (*grads, *[None] * (len(inputs) + 1))
+
+
 class _MIFn(torch.autograd.Function):
     """MutualInformation of single-channel image pairs without the reference's (B, H W, K) kernel-value
     tensors: ddrr_mi_forward / ddrr_mi_backward (include/diffdrr_mi_hip.h).  x1, x2 (B or 1, H, W) -> (B,)
@@ -331,14 +343,7 @@ class _MIFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x1, x2, bins, sigma, state = ctx.saved_tensors
-        B = ctx.B
-        grads = [None, None]
-        for which, x in ((0, x1), (1, x2)):
-            if ctx.needs_input_grad[which]:
-                gx = ops.mi_backward(x1, x2, bins, sigma, state, g, which, B)
-                grads[which] = gx.sum(0, keepdim=True) if (x.shape[0] == 1 and B != 1) else gx
-        return grads[0], grads[1], None, None, None, None, None
+        return _mi_image_grads(ctx, g, ops.mi_backward)
 
 
 def mutual_information(x1, x2, bins, sigma, epsilon=1e-10, normalize=True):
@@ -376,14 +381,7 @@ class _WeightedMIFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x1, x2, w, bins, sigma, state = ctx.saved_tensors
-        B = ctx.B
-        grads = [None, None]
-        for which, x in ((0, x1), (1, x2)):
-            if ctx.needs_input_grad[which]:
-                gx = ops.wmi_backward(x1, x2, w, bins, sigma, state, g, which, B)
-                grads[which] = gx.sum(0, keepdim=True) if (x.shape[0] == 1 and B != 1) else gx
-        return grads[0], grads[1], None, None, None, None, None, None
+        return _mi_image_grads(ctx, g, ops.wmi_backward)
 
 
 def weighted_mutual_information(x1, x2, weight, bins, sigma, epsilon=1e-10, normalize=True):
@@ -450,33 +448,37 @@ class MutualInformation(torch.nn.Module):
             raise ValueError(f"Input images must be the same size: {tuple(x1.shape)} and {tuple(x2.shape)}")
         if x1.dim() != 4 or x1.shape[1] != 1:
             raise ValueError(f"MutualInformation takes (B, 1, H, W) images, got {tuple(x1.shape)}")
-        B, _, H, W = x1.shape
-        K = self.bins.numel()
         if weight is not None:
             return self._weighted(x1, x2, weight)
-        if (ops.on_device(x2) and x1.device == x2.device == self.bins.device == self.sigma.device
-                and x1.dtype == x2.dtype == self.bins.dtype == self.sigma.dtype == torch.float32
-                and self.sigma.numel() == 1 and 1 <= K <= _lib.MI_MAX_BINS and H * W > 0
-                and not (torch.is_grad_enabled() and (self.bins.requires_grad or self.sigma.requires_grad))):
-            # an `expand`ed image (the fixed one, usually) is read once per pose from the same memory
-            a = x1[:1, 0] if (B > 1 and x1.stride(0) == 0) else x1[:, 0]
-            b = x2[:1, 0] if (B > 1 and x2.stride(0) == 0) else x2[:, 0]
+        if self._fused(x1, x2):
             # (the batch size is passed: both images may be expanded)
-            return _MIFn.apply(a, b, self.bins, self.sigma, float(self.epsilon), bool(self.normalize), B)
+            return _MIFn.apply(*self._images(x1, x2), self.bins, self.sigma, float(self.epsilon),
+                               bool(self.normalize), x1.shape[0])
         return mutual_information(x1, x2, self.bins, self.sigma, self.epsilon, self.normalize)
+
+    def _fused(self, x1, x2, *weight):
+        """Whether the kernels serve the call: float32 images, buffers (and weight) on the device, a bin count
+        the library takes, and no gradient wanted for anything but the images."""
+        H, W = x2.shape[-2:]
+        buffers = (self.bins, self.sigma, *weight)
+        return (ops.on_device(x2) and all(t.device == x2.device and t.dtype == torch.float32 for t in (x1, x2, *buffers))
+                and self.sigma.numel() == 1 and H * W > 0
+                and 1 <= self.bins.numel() <= (_lib.WMI_MAX_BINS if weight else _lib.MI_MAX_BINS)
+                and not (torch.is_grad_enabled() and any(t.requires_grad for t in buffers)))
+
+    @staticmethod
+    def _images(x1, x2):
+        """(B | 1, H, W) of each: an `expand`ed image (the fixed one, usually) is read once per pose from the same
+        memory"""
+        B = x2.shape[0]
+        return tuple(x[:1, 0] if (B > 1 and x.stride(0) == 0) else x[:, 0] for x in (x1, x2))
 
     def _weighted(self, x1, x2, weight):
         B, _, H, W = x2.shape
-        K = self.bins.numel()
         if weight.dim() != 4 or weight.shape[0] not in (1, B) or tuple(weight.shape[1:]) != (1, H, W):
             raise ValueError(f"weight has shape {tuple(weight.shape)}: (1 | {B}, 1, {H}, {W}) expected")
-        if (ops.on_device(x2) and x1.device == x2.device == weight.device == self.bins.device == self.sigma.device
-                and x1.dtype == x2.dtype == weight.dtype == self.bins.dtype == self.sigma.dtype == torch.float32
-                and self.sigma.numel() == 1 and 1 <= K <= _lib.WMI_MAX_BINS and H * W > 0
-                and not (torch.is_grad_enabled() and (self.bins.requires_grad or self.sigma.requires_grad
-                                                      or weight.requires_grad))):
-            a = x1[:1, 0] if (B > 1 and x1.stride(0) == 0) else x1[:, 0]
-            b = x2[:1, 0] if (B > 1 and x2.stride(0) == 0) else x2[:, 0]
+        if self._fused(x1, x2, weight):
+            a, b = self._images(x1, x2)
             # (one weight for the batch, given so or `expand`ed, is read in place)
             w = weight[:1, 0] if (weight.shape[0] == 1 or (B > 1 and weight.stride(0) == 0)) else weight[:, 0]
             return _WeightedMIFn.apply(a, b, w.detach(), self.bins, self.sigma, float(self.epsilon),

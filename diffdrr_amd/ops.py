@@ -1524,59 +1524,13 @@ def _mi_image(x, B, N):
     return x.contiguous(), N
 
 
-def mi_forward(x1, x2, bins, sigma, epsilon, normalize, B, want_state=True):
-    """MutualInformation (reference metrics.py:110-139) of B image pairs: x1, x2 (B or 1, H, W) fp32 on the
-    device (either or both may be ONE image shared by the batch: the batch size is B, not derived from the
-    shapes); bins (K,), sigma (0-dim): the module's buffers, read on the device.
-    -> (mi (B), state (B, S) | None: what :func:`mi_backward` needs)."""
-    _require_gpu(x2)
-    for x in (x1, x2):
-        if x.shape[0] not in (1, B):
-            raise ValueError(f"image batch {x.shape[0]} is neither 1 nor B = {B}")
-    H, W = x2.shape[-2:]
-    K = bins.numel()
-    a, s1 = _mi_image(x1, B, H * W)
-    b, s2 = _mi_image(x2, B, H * W)
-    bins, sigma = bins.contiguous(), sigma.contiguous()
-    dev = x2.device
-    out = torch.empty(B, dtype=torch.float32, device=dev)
-    state = None
-    if want_state:
-        state = torch.empty(B, int(_lib.get_mi_lib().query("ddrr_mi_state_floats", K)), dtype=torch.float32,
-                            device=dev)
-    if B:
-        n = int(_lib.get_mi_lib().query("ddrr_mi_workspace_bytes", B, H, W, K))
-        if n < 0:
-            raise ValueError(_lib.get_mi_lib()._last_error().decode(errors="replace"))
-        ws = torch.empty((n + 15) // 16, 4, dtype=torch.float32, device=dev)  # (16-byte aligned)
-        _launch_on(_lib.get_mi_lib(), "ddrr_mi_forward", dev, (
-            a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), K, sigma.data_ptr(), float(epsilon),
-            int(bool(normalize)), ws.data_ptr(), ws.numel() * 4, out.data_ptr(), _ptr(state)))
-    return out, state
-
-
-def mi_backward(x1, x2, bins, sigma, state, g_out, which, B):
-    """g_out[b] * d mi[b] / d x2[b] (which = 1) or / d x1[b] (which = 0), (B, H, W), of :func:`mi_forward`
-    with the same arguments.  A shared differentiated image gets its per-pose gradients (B, H, W)."""
-    H, W = x2.shape[-2:]
-    a, s1 = _mi_image(x1, B, H * W)
-    b, s2 = _mi_image(x2, B, H * W)
-    g_out, g_stride = _batch_grad(g_out, B)
-    grad = torch.empty(B, H, W, dtype=torch.float32, device=x2.device)
-    if B:
-        _launch_on(_lib.get_mi_lib(), "ddrr_mi_backward", x2.device, (
-            a.data_ptr(), s1, b.data_ptr(), s2, B, H, W, bins.data_ptr(), bins.numel(), sigma.data_ptr(),
-            state.data_ptr(), int(which), g_out.data_ptr(), g_stride, grad.data_ptr()))
-    return grad
-
-
-# ------------------------------------------------------------------ weighted MutualInformation (libdiffdrr_wmi_hip.so)
 def _launch_wmi(name, device, *args):
-    """:func:`_launch` through the weighted MutualInformation library."""
+    """:func:`_launch` through the weighted MutualInformation library (libdiffdrr_wmi_hip.so)."""
     _launch_on(_lib.get_wmi_lib(), name, device, args)
 
 
 def _query_wmi(name, *args):
+    # (not called here: the seam tests/test_wmi_abi.py uses to see a missing library fail loudly)
     return _lib.get_wmi_lib().query(name, *args)
 
 
@@ -1589,18 +1543,26 @@ def _wmi_weight(name, w, B, H, W):
     return _mi_image(w, B, H * W)
 
 
-def wmi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state=True, want_weight_sum=False):
-    """:func:`mi_forward` under per-pixel weights w (B or 1, H, W) float32, >= 0 and finite (not looked for;
-    include/diffdrr_wmi_hip.h): pixels with w == 0 are not read, a pair whose weights are all 0 scores 0.
-    -> (mi (B), state (B, S) | None: what :func:`wmi_backward` needs[, the pairs' sums of weights (B) float64,
-    with ``want_weight_sum``])."""
+def _mi_library(w):
+    """(entry prefix, library, launcher) that serve a call without / with a weight"""
+    if w is None:
+        lib = _lib.get_mi_lib()
+        return "ddrr_mi", lib, lambda name, device, *args: _launch_on(lib, name, device, args)
+    return "ddrr_wmi", _lib.get_wmi_lib(), _launch_wmi
+
+
+def _mi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state, want_weight_sum=False):
+    """:func:`mi_forward` (w None) and :func:`wmi_forward` -> (mi, state | None, weight_sum | None); the weighted
+    entry takes the weight and its stride after the images and `weight_sum` after `state`."""
     _require_gpu(x2)
     for x in (x1, x2):
         if x.shape[0] not in (1, B):
             raise ValueError(f"image batch {x.shape[0]} is neither 1 nor B = {B}")
     H, W = x2.shape[-2:]
     K = bins.numel()
-    wt, sw = _wmi_weight("wmi_forward", w, B, H, W)
+    wt, sw = (None, None) if w is None else _wmi_weight("wmi_forward", w, B, H, W)
+    wargs = () if w is None else (wt.data_ptr(), sw)
+    prefix, lib, launch = _mi_library(w)
     a, s1 = _mi_image(x1, B, H * W)
     b, s2 = _mi_image(x2, B, H * W)
     bins, sigma = bins.contiguous(), sigma.contiguous()
@@ -1608,34 +1570,65 @@ def wmi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state=True, 
     out = torch.empty(B, dtype=torch.float32, device=dev)
     state = None
     if want_state:
-        state = torch.empty(B, int(_query_wmi("ddrr_wmi_state_floats", K)), dtype=torch.float32, device=dev)
+        state = torch.empty(B, int(lib.query(prefix + "_state_floats", K)), dtype=torch.float32, device=dev)
     weight_sum = torch.empty(B, dtype=torch.float64, device=dev) if want_weight_sum else None
     if B:
-        n = int(_query_wmi("ddrr_wmi_workspace_bytes", B, H, W, K))
+        n = int(lib.query(prefix + "_workspace_bytes", B, H, W, K))
         if n < 0:
-            raise ValueError(_lib.get_wmi_lib()._last_error().decode(errors="replace"))
+            raise ValueError(lib._last_error().decode(errors="replace"))
         ws = torch.empty((n + 15) // 16, 4, dtype=torch.float32, device=dev)  # (16-byte aligned)
-        _launch_wmi("ddrr_wmi_forward", dev, a.data_ptr(), s1, b.data_ptr(), s2, wt.data_ptr(), sw, B, H, W,
-                    bins.data_ptr(), K, sigma.data_ptr(), float(epsilon), int(bool(normalize)), ws.data_ptr(),
-                    ws.numel() * 4, out.data_ptr(), _ptr(state), _ptr(weight_sum))
-    return (out, state, weight_sum) if want_weight_sum else (out, state)
+        launch(prefix + "_forward", dev, a.data_ptr(), s1, b.data_ptr(), s2, *wargs, B, H, W, bins.data_ptr(), K,
+               sigma.data_ptr(), float(epsilon), int(bool(normalize)), ws.data_ptr(), ws.numel() * 4, out.data_ptr(),
+               _ptr(state), *(() if w is None else (_ptr(weight_sum),)))
+    return out, state, weight_sum
+
+
+def _mi_backward(x1, x2, w, bins, sigma, state, g_out, which, B):
+    """:func:`mi_backward` (w None) and :func:`wmi_backward`"""
+    H, W = x2.shape[-2:]
+    wt, sw = (None, None) if w is None else _wmi_weight("wmi_backward", w, B, H, W)
+    wargs = () if w is None else (wt.data_ptr(), sw)
+    prefix, _, launch = _mi_library(w)
+    a, s1 = _mi_image(x1, B, H * W)
+    b, s2 = _mi_image(x2, B, H * W)
+    g_out, g_stride = _batch_grad(g_out, B)
+    grad = torch.empty(B, H, W, dtype=torch.float32, device=x2.device)
+    if B:
+        launch(prefix + "_backward", x2.device, a.data_ptr(), s1, b.data_ptr(), s2, *wargs, B, H, W, bins.data_ptr(),
+               bins.numel(), sigma.data_ptr(), state.data_ptr(), int(which), g_out.data_ptr(), g_stride,
+               grad.data_ptr())
+    return grad
+
+
+def mi_forward(x1, x2, bins, sigma, epsilon, normalize, B, want_state=True):
+    """MutualInformation (reference metrics.py:110-139) of B image pairs: x1, x2 (B or 1, H, W) fp32 on the
+    device (either or both may be ONE image shared by the batch: the batch size is B, not derived from the
+    shapes); bins (K,), sigma (0-dim): the module's buffers, read on the device.
+    -> (mi (B), state (B, S) | None: what :func:`mi_backward` needs)."""
+    return _mi_forward(x1, x2, None, bins, sigma, epsilon, normalize, B, want_state)[:2]
+
+
+def mi_backward(x1, x2, bins, sigma, state, g_out, which, B):
+    """g_out[b] * d mi[b] / d x2[b] (which = 1) or / d x1[b] (which = 0), (B, H, W), of :func:`mi_forward`
+    with the same arguments.  A shared differentiated image gets its per-pose gradients (B, H, W)."""
+    return _mi_backward(x1, x2, None, bins, sigma, state, g_out, which, B)
+
+
+# ------------------------------------------------------------------ weighted MutualInformation (libdiffdrr_wmi_hip.so)
+def wmi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state=True, want_weight_sum=False):
+    """:func:`mi_forward` under per-pixel weights w (B or 1, H, W) float32, >= 0 and finite (not looked for;
+    include/diffdrr_wmi_hip.h): pixels with w == 0 are not read, a pair whose weights are all 0 scores 0.
+    -> (mi (B), state (B, S) | None: what :func:`wmi_backward` needs[, the pairs' sums of weights (B) float64,
+    with ``want_weight_sum``])."""
+    res = _mi_forward(x1, x2, w, bins, sigma, epsilon, normalize, B, want_state, want_weight_sum)
+    return res if want_weight_sum else res[:2]
 
 
 def wmi_backward(x1, x2, w, bins, sigma, state, g_out, which, B):
     """g_out[b] * d mi[b] / d x2[b] (which = 1) or / d x1[b] (which = 0), (B, H, W), of :func:`wmi_forward`
     with the same arguments; exactly 0 where w == 0.  A shared differentiated image gets its per-pose gradients
     (B, H, W)."""
-    H, W = x2.shape[-2:]
-    wt, sw = _wmi_weight("wmi_backward", w, B, H, W)
-    a, s1 = _mi_image(x1, B, H * W)
-    b, s2 = _mi_image(x2, B, H * W)
-    g_out, g_stride = _batch_grad(g_out, B)
-    grad = torch.empty(B, H, W, dtype=torch.float32, device=x2.device)
-    if B:
-        _launch_wmi("ddrr_wmi_backward", x2.device, a.data_ptr(), s1, b.data_ptr(), s2, wt.data_ptr(), sw, B, H, W,
-                    bins.data_ptr(), bins.numel(), sigma.data_ptr(), state.data_ptr(), int(which), g_out.data_ptr(),
-                    g_stride, grad.data_ptr())
-    return grad
+    return _mi_backward(x1, x2, w, bins, sigma, state, g_out, which, B)
 
 
 # ------------------------------------------------------------------ reconstruction (libdiffdrr_recon_hip.so)

@@ -3,7 +3,7 @@
  * collimator, a confidence map) as fused gfx950 kernels.  The unweighted criterion is include/diffdrr_mi_hip.h.
  *
  * A library of its own, next to libdiffdrr_mi_hip.so: the two share no symbol, no state and no version
- * number.  The kernels are csrc/mi.hip's with the weight added, at mi.hip's launch geometry.
+ * number.  Both instantiate the kernel bodies of csrc/mi_kernels.h, this one with the weight, at one launch geometry.
  *
  * What is computed, per image pair b (N = H W pixels, K = num_bins bins, w >= 0 and finite -- not looked for):
  *   V = {n: w[n] != 0},  Sw = sum_V w[n]
